@@ -18,9 +18,14 @@ scaling), cfg5 (Monte-Carlo sweep, 262 144 filters in all with device-drawn per-
 per-device RMSE reduction combined on the host; --batch-per-gpu B runs one B-filter shard per rank instead),
 cfg3mr (cfg3 with the multirate delayed-measurement replay).
 
-The K-step timed region is bracketed by barrier + device synchronise on both sides; when it is shorter than ~20 ms it
-is repeated (`repeats`) and the median region (max over ranks of each) is reported, so that `value` does not carry the
-~45 us synchronisation tail of a single sub-millisecond region.
+The K-step timed region is bracketed by barrier + device synchronise on both sides and runs exactly K steps.  The W
+warmup steps before it cover at least one whole measurement period, so that every kernel of the schedule has been
+loaded and launched once before the clock starts.  --repeats R > 1 times R such regions back to back (R x K timed steps)
+and reports the median region (max over ranks of each).
+
+--dump-outputs DIR writes what the timed path computed, the state (x, P) after its last step as get_state() returns it,
+to DIR/*.npy (float64; a fixed, seeded sample of the filters when the whole state exceeds 64 MB).  The inputs depend only
+on the arguments, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -204,6 +209,28 @@ def sub_record(qla, cfg, B, dtype, upd, n_pred, n_mixed, seed, device):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # all ranks' files together
+DUMP_SAMPLE_SEED = 0xD0517
+
+
+def dump_outputs(ekf, out_dir, rank, world):
+    """The state the timed path left behind (get_state(): x [B,16], P [B,n,n], float64) -> out_dir/{x,P,filter_index}.npy.  When the
+    whole state is over this rank's share of the budget, a fixed seeded sample of the filters (sorted) is written; filter_index holds
+    their indices within the rank's shard.  With N > 1 ranks every file name carries a _rank<r> suffix."""
+    x, P = ekf.get_state()
+    B = x.shape[0]
+    per_filter = x[0].nbytes + P[0].nbytes + 8
+    n = min(B, (DUMP_BUDGET_BYTES // max(world, 1)) // per_filter)
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, size=n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    arrays = {"x": x[idx], "P": P[idx], "filter_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "files": sorted(f"{k}{sfx}.npy" for k in arrays), "filters": int(n), "of": int(B), "sampled": bool(n < B),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def self_launch(n, stdout_fd):
     """Run this script as n ranks (one per GPU) under torch.distributed.run and return the launcher's exit code."""
     import socket
@@ -231,8 +258,9 @@ def main():
     os.dup2(2, 1)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=4000)
-    ap.add_argument("--warmup", type=int, default=60)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 4000; cfg2 1000; rotors / hardware 1400)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps first, at least one measurement period (default 60; cfg2 20; "
+                                                              "rotors / hardware 70)")
     ap.add_argument("--batch-per-gpu", type=int, default=0, help="filters per rank (weak scaling); default: the workload's own size")
     ap.add_argument("--global-batch", type=int, default=0, help="filters in all, split over the ranks (strong scaling); default for cfg4 / cfg5")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
@@ -241,9 +269,13 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the hbm_resident / f64_same_batch sub-records and the on-chip-resident variant")
     ap.add_argument("--kernel-steps", "--predict-only-steps", type=int, default=2000, dest="kernel_steps",
                     help="back-to-back launches of the dominant kernel for the roofline record")
-    ap.add_argument("--repeats", type=int, default=0, help="repetitions of the K-step timed region (0 = as many as make ~20 ms, at most 25)")
+    ap.add_argument("--repeats", type=int, default=1, help="timed regions of K steps each (R x K timed steps in all); the median is reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state after the last timed step to DIR/*.npy")
     ap.add_argument("--workload", default="cfg3", choices=list(WORKLOADS))
     args = ap.parse_args()
+    if args.repeats < 1:
+        ap.error("--repeats must be >= 1")
+    steps_default, warmup_default = 4000, 60
     cfg = dict(CFG3)
     upd = 14  # ceil(400/30), relative_pose_EKF.cpp:91
     perturb = False
@@ -254,8 +286,7 @@ def main():
         upd = 1
         args.dtype = "f64"
         per_gpu_default = 4096
-        if args.steps == 4000:
-            args.steps, args.warmup = 1000, 20
+        steps_default, warmup_default = 1000, 20
     elif args.workload == "cfg4":
         global_default = 1048576
     elif args.workload == "cfg5":
@@ -272,13 +303,20 @@ def main():
         cfg = {}
         upd = int(der.upd_per_meas)                                   # ceil(update_freq / measurement_freq), EKF.cpp:91
         mr_step = int(der.measurement_step_delay)                     # int(measurement_delay / dT + 0.5), EKF.cpp:93
-        if args.steps == 4000:
-            args.steps, args.warmup = 1400, 70
+        steps_default, warmup_default = 1400, 70
     if args.workload == "cfg3mr":
         # delays of relative_pose_EKF_rotors.yaml:5-7 at 400 Hz: step delay int(0.030/0.0025 + 0.5) = 12 ticks
         cfg.update(multirate_ekf=1, dynamic_meas_delay=1, measurement_delay=0.030, measurement_delay_max=0.200,
                    dyn_measurement_delay_offset=0.005)
         mr_step = 12
+    if args.steps is None:
+        args.steps = steps_default
+    if args.warmup is None:
+        args.warmup = warmup_default
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    # a warmup shorter than one measurement period would leave the fused tick's kernel to be loaded inside the timed region
+    args.warmup = max(args.warmup, upd)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -355,19 +393,18 @@ def main():
         barrier()
         return w, ev
 
+    ekf.timer_begin()        # the warmup goes through the timer too, so that the timed region is not its first use
     ekf.run(seq, 0, W)
+    ekf.timer_end()
     ekf.synchronize()
     pos = W
     regions = [timed_region(pos)]
     pos += K
-    R = args.repeats or int(min(25, max(1, np.ceil(0.020 / max(regions[0][0], 1e-6)))))
-    if dist is not None:   # every rank must run the same number of regions
-        rt = torch.tensor([R], dtype=torch.int64)
-        dist.all_reduce(rt, op=dist.ReduceOp.MAX)
-        R = int(rt[0])
+    R = args.repeats
     for _ in range(R - 1):
         regions.append(timed_region(pos))
         pos += K
+    dumped = dump_outputs(ekf, args.dump_outputs, rank, world) if args.dump_outputs else None
     walls = np.array([r[0] for r in regions]); evs = np.array([r[1] for r in regions])
     per_rank = None
     if dist is not None:
@@ -459,7 +496,7 @@ def main():
         "metric": "EKF predict+update steps/sec at batch=65536; achieved HBM GB/s vs roofline",
         "value": global_batch * K / wall,
         "unit": "EKF ticks/s",
-        "n_gpus": world, "steps": K, "warmup": W, "repeats": R,
+        "n_gpus": world, "steps": K, "warmup": W, "repeats": R, "timed_steps": K * R,
         "ms_per_step": wall / K * 1e3,
         "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
         "dtype": args.dtype, "data": "synthetic",
@@ -507,6 +544,8 @@ def main():
                                 "wraps_in_timed_regions": int(wraps)}
     if per_rank is not None:
         out["per_rank"] = per_rank
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if resident is not None:
         out["on_chip_resident"] = resident
     if x0 is not None:

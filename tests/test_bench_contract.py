@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,3 +173,59 @@ def test_bench_strong_scaling_workloads_split_a_fixed_global_batch(workload, glo
     assert d["nonfinite_filters"] == 0
     if workload == "cfg5":
         assert d["rmse_vs_truth"]["filters"] == glob     # the three sums of both devices combined on the host
+
+
+class _FakeState:
+    """get_state() of a handle without a GPU: a deterministic state of B filters."""
+    def __init__(self, B, n=15):
+        self.x = np.arange(B * 16, dtype=np.float64).reshape(B, 16)
+        self.P = np.broadcast_to(np.arange(B, dtype=np.float64)[:, None, None], (B, n, n)).copy()
+
+    def get_state(self):
+        return self.x, self.P
+
+
+def test_dump_outputs_writes_the_whole_state_or_a_fixed_sample_within_the_budget(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    small = _FakeState(100)
+    info = bench.dump_outputs(small, str(tmp_path / "small"), 0, 1)
+    assert not info["sampled"] and info["filters"] == 100
+    assert sorted(os.listdir(tmp_path / "small")) == ["P.npy", "filter_index.npy", "x.npy"]
+    x = np.load(tmp_path / "small" / "x.npy")
+    assert x.dtype == np.float64 and np.array_equal(x, small.x)
+    big = _FakeState(40000)     # 77 MB of state: over the 64 MB budget
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"big{k}"
+        info = bench.dump_outputs(big, str(d), 0, 1)
+        assert info["sampled"] and 0 < info["filters"] < 40000
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 * 10 ** 6
+        runs.append({f: np.load(d / f) for f in os.listdir(d)})
+    idx = runs[0]["filter_index.npy"].astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(runs[0]["x.npy"], big.x[idx]) and np.array_equal(runs[0]["P.npy"], big.P[idx])
+    assert all(np.array_equal(runs[0][f], runs[1][f]) for f in runs[0])     # the same sample every time
+    info = bench.dump_outputs(small, str(tmp_path / "ranks"), 1, 2)
+    assert info["files"] == ["P_rank1.npy", "filter_index_rank1.npy", "x_rank1.npy"]
+
+
+@pytest.mark.gpu
+def test_bench_steps_are_the_timed_steps_and_dumped_outputs_repeat(tmp_path):
+    """--steps K times exactly K ticks (one region by default), and two runs with the same arguments dump the same state."""
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "23", "--warmup", "5", "--batch-per-gpu", "4096",
+               "--kernel-steps", "60", "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(r.stdout.strip())
+        assert d["steps"] == 23 and d["repeats"] == 1 and d["timed_steps"] == 23
+        assert sum(d["roofline"]["mixed_kernels"].values()) == 23
+        assert d["warmup"] == 14          # raised to one measurement period so that the fused tick's kernel is loaded before the clock
+        assert d["dumped_outputs"]["filters"] == 4096 and not d["dumped_outputs"]["sampled"]
+        arrs = {f: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert sorted(arrs) == ["P.npy", "filter_index.npy", "x.npy"]
+        assert arrs["x.npy"].shape == (4096, 16) and arrs["x.npy"].dtype == np.float64 and np.isfinite(arrs["P.npy"]).all()
+        dumps.append(arrs)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
