@@ -130,6 +130,19 @@ def structured_quat_exp(v, dtype="f64"):
     return q
 
 
+def structured_half_angle_wave(h2, dtype="f64", wave=64):
+    """half_angle_sinc_cos of the engine (ekf_device.hpp compiled for the host) on half-angles squared h2 [n], with consecutive
+    groups of `wave` elements run as one device wave (the loops' trip count is the group's largest halving count).
+    Returns (k, ch) = (sin(h) / (2 h), cos(h))."""
+    L = _structured_lib()
+    h2 = np.ascontiguousarray(h2, dtype=np.float64).reshape(-1)
+    k = np.empty_like(h2); ch = np.empty_like(h2)
+    L.orc_structured_half_angle_wave.argtypes = [C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.c_int64, _i, C.c_int64]
+    L.orc_structured_half_angle_wave.restype = None
+    L.orc_structured_half_angle_wave(_p(h2), _p(k), _p(ch), h2.shape[0], 0 if dtype == "f32" else 1, int(wave))
+    return k, ch
+
+
 def structured_run_batch(p, x, P, u, z=None, mask=None, dtype="f64", levels=True, n_threads=0):
     """The engine's own per-filter arithmetic (quadrotor_landing_amd/csrc/ekf_device.hpp) compiled for the CPU:
     same contract as run_batch.  Second CPU baseline and no-GPU algebra check; never part of the product.

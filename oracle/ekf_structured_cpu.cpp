@@ -255,6 +255,34 @@ void orc_structured_quat_exp(const double* v, double* q, int64_t n, int dtype)
         }
     }
 }
+// half_angle_sinc_cos (ekf_device.hpp) for n half-angles squared h2, as the device runs it: consecutive groups of `wave` elements are
+// one wave, whose loops run as many rounds as its largest per-lane halving count (restated here: quarter while finite and > (pi/4)^2).
+// wave = 1 is the per-element host form.  k = sin(h) / (2 h), ch = cos(h).
+void orc_structured_half_angle_wave(const double* h2, double* k, double* ch, int64_t n, int dtype, int64_t wave)
+{
+    for (int64_t w0 = 0; w0 < n; w0 += wave) {
+        const int64_t w1 = w0 + wave < n ? w0 + wave : n;
+        int rounds = 0;
+        for (int64_t i = w0; i < w1; ++i) {
+            int r = 0;
+            if (dtype == 0) {
+                for (float h = (float)h2[i]; h > 0.6168502750680849f && h <= 3.4028234663852886e38f; h *= 0.25f) ++r;
+            } else {
+                for (double h = h2[i]; h > 0.6168502750680849 && h <= 1.7976931348623157e308; h *= 0.25) ++r;
+            }
+            rounds = r > rounds ? r : rounds;
+        }
+        for (int64_t i = w0; i < w1; ++i) {
+            if (dtype == 0) {
+                float kk, cc;
+                half_angle_sinc_cos<float>((float)h2[i], kk, cc, rounds);
+                k[i] = kk; ch[i] = cc;
+            } else {
+                half_angle_sinc_cos<double>(h2[i], k[i], ch[i], rounds);
+            }
+        }
+    }
+}
 // The quad arithmetic (ekf_quad.hpp) on an emulated quad; same contract as orc_run_batch.
 int64_t orc_quad_run_batch(const orc_params* p, int64_t B, int64_t T, double* x, double* P, const double* u, const double* z,
                            const uint8_t* mask, int dtype)

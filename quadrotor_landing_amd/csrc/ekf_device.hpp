@@ -167,20 +167,36 @@ struct Noise {
 // sin(h) / (2 h) and cos(h): the vector scale and the scalar part of exp(phi), h = |phi| / 2 (QH.cpp:9-28).  Series in h^2 on
 // |h| <= pi/4 (truncation < 3e-10 in fp32, < 3e-20 in fp64).  Larger half-angles (no physical rate: more than 90 degrees per tick) are
 // halved until they fit and the result is doubled back -- sin 2a / 2a = (sin a / a) cos a, cos 2a = 1 - 2 a^2 (sin a / a)^2, no square
-// root.  The number of halvings is WAVE-UNIFORM (the largest any lane needs; normally zero, and then nothing below differs from the
-// plain series): a per-lane branch to the library's sincos here put a divergent region into the middle of kernels that sit at the
-// register limit, and the backend placed register copies at that region's join in front of the EXEC restore -- copies that never
-// happened for the lanes that had skipped the branch (profiles/r04_tuning.md section 1: the GPU memory access faults).
+// root.  The number of halvings is PER LANE, the control flow WAVE-UNIFORM: the loops run as long as the wave's largest count needs
+// (normally zero: one vote, nothing else) and every lane applies a step through a select only while its own count lasts, so a lane
+// that needs no halving produces exactly the plain-series bits whatever its neighbours hold.  A non-finite h2 takes no part in the
+// vote and comes out non-finite for its own lane only (as sin(Inf) does in the reference).  The trip count is capped at what the
+// largest finite h2 needs (65 in fp32, 513 in fp64), so the cap never binds.  No per-lane branch: a branch to the library's sincos
+// here put a divergent region into the middle of kernels that sit at the register limit, and the backend placed register copies at
+// that region's join in front of the EXEC restore -- copies that never happened for the lanes that had skipped the branch
+// (profiles/r04_tuning.md section 1: the GPU memory access faults).
+// host_wave_rounds (host build only; the device ignores it): the trip count the other lanes of an emulated wave force on this
+// element, so that a host build can run the device's mixed-wave semantics (one emulated wave at a time).
 template <typename T>
-__host__ __device__ __forceinline__ void half_angle_sinc_cos(T h2, T& k, T& ch)
+__host__ __device__ __forceinline__ void half_angle_sinc_cos(T h2, T& k, T& ch, int host_wave_rounds = 0)
 {
     constexpr T kLim = T(0.6168502750680849);   // (pi/4)^2
-    int halvings = 0;
+    constexpr T kMax = sizeof(T) == 4 ? T(3.4028234663852886e38) : T(1.7976931348623157e308);   // largest finite value
+    constexpr int kCap = sizeof(T) == 4 ? 65 : 513;   // ceil(log4(kMax / kLim)): quarterings the largest finite h2 needs
+    bool big = h2 > kLim && h2 <= kMax;         // false for NaN and Inf
+    int n = 0;                                  // this lane's halvings
+    int rounds = 0;                             // the wave's largest n (the host build: this element's)
 #if defined(__HIP_DEVICE_COMPILE__)
-    while (halvings < 600 && __any(h2 > kLim)) { h2 *= T(0.25); ++halvings; }
+    (void)host_wave_rounds;
+    while (rounds < kCap && __any(big)) {
 #else
-    while (halvings < 600 && h2 > kLim) { h2 *= T(0.25); ++halvings; }
+    while (rounds < kCap && (big || rounds < host_wave_rounds)) {
 #endif
+        h2 = big ? h2 * T(0.25) : h2;
+        n += big ? 1 : 0;
+        ++rounds;
+        big = h2 > kLim && h2 <= kMax;
+    }
     T sc, cc;   // sin(a) / a and cos(a), a^2 = h2
     if (sizeof(T) == 4) {
         // sin h / h = 1 - h2/6 + h2^2/120 - h2^3/5040 + h2^4/362880 - h2^5/39916800
@@ -224,11 +240,19 @@ __host__ __device__ __forceinline__ void half_angle_sinc_cos(T h2, T& k, T& ch)
         c = c * h2 + T(-0.5);
         cc = c * h2 + T(1);
     }
-    for (int j = 0; j < halvings; ++j) {   // wave-uniform trip count
+    for (int j = 0; j < rounds; ++j) {     // wave-uniform trip count, step j applied only where j < n
+        const bool on = j < n;
         const T s2 = sc * sc * h2;
-        sc = sc * cc;
-        cc = T(1) - T(2) * s2;
-        h2 = h2 * T(4);
+        const T h2d = h2 * T(4);
+        T sd = sc * cc;
+        T cd = T(1) - T(2) * s2;
+        // back onto the unit circle: sin^2 + cos^2 - 1 grows up to 4x per doubling (4 sin^2 times it), 4^64 over the fp32 cap
+        const T r = T(1) / t_sqrt(sd * sd * h2d + cd * cd);
+        sd = sd * r;
+        cd = cd * r;
+        sc = on ? sd : sc;
+        cc = on ? cd : cc;
+        h2 = on ? h2d : h2;
     }
     k = T(0.5) * sc;
     ch = cc;
@@ -247,7 +271,7 @@ __device__ __forceinline__ void quat_norm(T (&q)[4])
 
 // quaternion_exp, QH.cpp:9-33 (including the final quaternion_norm at :30).
 // sin(|v|/2)/|v| and cos(|v|/2) come from half_angle_sinc_cos: the series the reference's small-angle branch truncates (QH.cpp:19-24),
-// valid for every |v| <= pi/2 without a square root, a division or a branch; larger arguments take the library path inside it.
+// valid for every |v| <= pi/2 without a square root, a division or a branch; larger arguments are halved and doubled back inside it.
 template <typename T>
 __device__ __forceinline__ void quat_exp(const T (&v)[3], T (&q)[4])
 {

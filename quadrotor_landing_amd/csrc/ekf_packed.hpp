@@ -19,7 +19,7 @@
 //     reads only block-rows at or below its own and writes its own, so the whole step is in place (no second copy of P).
 //   * F[th,th] = AngleAxis(-|phi|, phi/|phi|) (EKF.cpp:383-395) is the rotation matrix of the conjugate of exp(phi), which the nominal
 //     state needs anyway (EKF.cpp:367): one half-angle sine / cosine per tick, as branch-free polynomials for |phi|/2 <= pi/4 (any
-//     physical rate: 0.79 rad per tick) with the libm path behind a wave-level branch beyond.  The small-angle branches of the
+//     physical rate: 0.79 rad per tick) and per-lane halving / doubling beyond (half_angle_sinc_cos).  The small-angle branches of the
 //     reference (QH.cpp:19-28, EKF.cpp:385-389) are the same series truncated; they agree to 1e-20.
 // ~900 instructions per tick in fp32 (of which ~330 packed) against ~1 370.  Device code runs the block form in fp32 only (k_step_mr<float>);
 // the fp64 replay keeps its covariance split between the LDS and registers (ekf_split.hpp) and the on-chip-resident kernel runs the in-place

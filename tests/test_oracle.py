@@ -436,6 +436,51 @@ def test_engine_quaternion_exp_large_angles_halving_and_doubling():
         assert np.abs(np.linalg.norm(q, axis=1) - 1).max() < (1e-15 if dtype == "f64" else 3e-7)
 
 
+def test_engine_half_angle_per_lane_halving_cap_and_non_finite_lanes():
+    """half_angle_sinc_cos (ekf_device.hpp, host build) at the edges of the halving: the largest finite half-angle still fits the
+    per-dtype trip-count cap (65 quarterings in fp32, 513 in fp64) and yields a finite unit quaternion; Inf / NaN inputs come out
+    non-finite on their own and leave every other element unchanged bit for bit.  The same with 64 elements run as one device wave
+    (oracle.structured_half_angle_wave: the loops run the wave's largest halving count): each lane's result equals the one it gets
+    alone, whatever its neighbours need -- large angles, the cap, Inf or NaN."""
+    rng = np.random.default_rng(17)
+    for dtype, big in (("f32", float(np.finfo(np.float32).max)), ("f64", float(np.finfo(np.float64).max))):
+        # the largest finite h2 and its neighbours: finite, |q| = 1 (|v|^2 = 4 h2, q = (v k, ch))
+        h2 = np.array([big, big / 2, big / 4, 1e30, 0.6168502750680849 * 4.0 ** 60])
+        k, ch = oracle.structured_half_angle_wave(h2, dtype, wave=1)
+        assert np.isfinite(k).all() and np.isfinite(ch).all(), (dtype, k, ch)
+        hq = h2.astype(np.float32).astype(np.float64) if dtype == "f32" else h2
+        nq2 = (2 * np.sqrt(hq) * k) ** 2 + ch * ch
+        assert np.abs(nq2 - 1).max() < (2e-6 if dtype == "f32" else 1e-14), (dtype, nq2)
+        # through quat_exp: |v|^2 / 4 just below the largest finite value (|v|^2 itself must not overflow)
+        v = rng.normal(size=(8, 3)); v *= (np.sqrt(big) * 0.999 / np.linalg.norm(v, axis=1))[:, None]
+        q = oracle.structured_quat_exp(v, dtype)
+        assert np.isfinite(q).all() and np.abs(np.linalg.norm(q, axis=1) - 1).max() < (3e-7 if dtype == "f32" else 1e-15), (dtype, q)
+
+        # mixed arrays: rotation angles 1e-12 .. 40 rad, the cap, and non-finite elements scattered over the waves
+        n = 64 * 8 + 23
+        ang = np.where(rng.uniform(size=n) < 0.2, rng.uniform(1.6, 40.0, n), 10 ** rng.uniform(-12, 0.15, n))
+        h2 = (ang / 2) ** 2
+        h2[[5, 64 + 63, 3 * 64 + 30, n - 2]] = big            # the cap next to plain-series lanes
+        bad = np.zeros(n, bool)
+        bad[[0, 63, 2 * 64 + 17, 5 * 64 + 40, 7 * 64 + 1, n - 1]] = True
+        h2b = h2.copy()
+        h2b[bad] = np.where(np.arange(bad.sum()) % 2 == 0, np.inf, np.nan)
+        ka, ca = oracle.structured_half_angle_wave(h2, dtype, wave=1)
+        for wave in (1, 64):
+            kb, cb = oracle.structured_half_angle_wave(h2b, dtype, wave=wave)
+            assert (~np.isfinite(kb[bad]) | ~np.isfinite(cb[bad])).all(), (dtype, wave)
+            np.testing.assert_array_equal(kb[~bad], ka[~bad]); np.testing.assert_array_equal(cb[~bad], ca[~bad])
+            kc, cc = oracle.structured_half_angle_wave(h2, dtype, wave=wave)   # finite neighbours only
+            np.testing.assert_array_equal(kc, ka); np.testing.assert_array_equal(cc, ca)
+        # and through quat_exp: Inf / NaN rotation vectors among finite ones
+        v = rng.normal(size=(n, 3)); v *= (ang / np.linalg.norm(v, axis=1))[:, None]
+        vb = v.copy()
+        vb[bad] = np.where((np.arange(bad.sum()) % 2 == 0)[:, None], np.array([np.inf, 0, 0]), np.array([0, np.nan, 1.0]))
+        qa, qb = oracle.structured_quat_exp(v, dtype), oracle.structured_quat_exp(vb, dtype)
+        assert np.isfinite(qa).all() and (~np.isfinite(qb[bad])).any(axis=1).all()
+        np.testing.assert_array_equal(qb[~bad], qa[~bad])
+
+
 def test_packed_covariance_order_is_a_bijection_with_level_structure():
     """sidx (ekf_device.hpp) restated: 120 distinct words, block-rows in storage order r, v, th, ab, wb quad-wise,
     memory quad 3m + l = the m-th quad of quad-lane l, and lane l holds column l of every off-diagonal block."""
