@@ -172,6 +172,28 @@ int qle_update(qle_batch *h, const double *z, const uint8_t *mask);
  * z/mask may be NULL for a predict-only tick. */
 int qle_step(qle_batch *h, const double *u, const double *z, const uint8_t *mask);
 
+/* ---- innovation diagnostics and a chi-square outlier gate -------------------
+ * correction_step forms the innovation delta_y (EKF.cpp:447-450) and its covariance S = G P G^T + R_k (EKF.cpp:475) and
+ * keeps neither.  These calls evaluate them on the device against the current state, together with the normalised
+ * innovation squared NIS = delta_y^T S^-1 delta_y: chi-square with 6 degrees of freedom for a consistent filter (mean 6;
+ * 16.81 and 22.46 are its 0.99 and 0.999 quantiles).  A filter with mask 0 or without state (qle_initialize_state_masked)
+ * gets nu = 0, S = 0, NIS = NaN and is never accepted; so is a filter whose S is not positive definite (NIS = NaN).
+ * The gated calls are the single-rate filter without the device decision logic: with multirate_ekf set or
+ * qle_enable_gating on they return QLE_ERR_STATE.  Follow-ups, not provided: a gate inside the multirate replay, a gate
+ * inside the decision logic of qle_filter_update, and a fused single-launch gated tick (qle_step_gated is three launches). */
+/* delta_y (EKF.cpp:447-450), S = G P G^T + R_k (EKF.cpp:475) and NIS of tag pose z = [batch][7]
+ * against the current state, where mask != 0 (NULL = all).  Reads the state, changes nothing.
+ * nu = [batch][6], S = [batch][36] (symmetric, row-major), nis = [batch]; any output may be NULL
+ * (all NULL: the results stay on the device and the call returns without synchronising).
+ * With multirate_ekf set it evaluates against the current state, not the history entry a delayed measurement belongs to. */
+int qle_innovation(qle_batch *h, const double *z, const uint8_t *mask, double *nu, double *S, double *nis);
+/* qle_update (correction_step, EKF.cpp:417-502) on the filters whose NIS <= chi2_max only; accepted = [batch],
+ * nis = [batch], either may be NULL.  chi2_max > 0; +INFINITY accepts every finite NIS. */
+int qle_update_gated(qle_batch *h, const double *z, const uint8_t *mask, double chi2_max, uint8_t *accepted, double *nis);
+/* qle_step (EKF.cpp:238-249 + 265-290) with the same gate between predict and correct. */
+int qle_step_gated(qle_batch *h, const double *u, const double *z, const uint8_t *mask, double chi2_max,
+                   uint8_t *accepted, double *nis);
+
 /* ---- the decision logic of filter_update on the device ----------------------
  * With gating enabled, the mask of qle_step / qle_filter_update / the mask word
  * of a sequence slot means "measurement_ready" (EKF.hpp:125), and the engine

@@ -102,6 +102,9 @@ SYMBOLS = {
     "qle_predict": (C.c_int, [_vp, _pd]),
     "qle_update": (C.c_int, [_vp, _pd, _pu8]),
     "qle_step": (C.c_int, [_vp, _pd, _pd, _pu8]),
+    "qle_innovation": (C.c_int, [_vp, _pd, _pu8, _pd, _pd, _pd]),
+    "qle_update_gated": (C.c_int, [_vp, _pd, _pu8, _d, _pu8, _pd]),
+    "qle_step_gated": (C.c_int, [_vp, _pd, _pd, _pu8, _d, _pu8, _pd]),
     "qle_enable_gating": (C.c_int, [_vp, _i32]),
     "qle_filter_update": (C.c_int, [_vp, _pd, _pd, _pu8]),
     "qle_filter_update_stamped": (C.c_int, [_vp, _pd, _pd, _pu8, _d, _pd]),

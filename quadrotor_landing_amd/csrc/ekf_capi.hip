@@ -4,6 +4,7 @@
 // reference), AoS<->quad-row staging, launches on the handle's own stream.
 // There is deliberately no CPU compute path in this file.
 #include "ekf_host.hpp"
+#include "ekf_innov.hpp"
 #include "synth_kernels.hpp"
 
 // ------------------------------------------------------------------ errors
@@ -206,7 +207,7 @@ extern "C" int qle_destroy(qle_batch* h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* bufs[] = {h->ring, h->pfp, h->aux_accel, h->aux_obs, h->tick_u, h->tick_z, h->stage, h->stage_mask, h->counter, h->last_corr, h->flags, h->hist_first, h->stamp,
-                    h->delay_cur, h->mr_u, h->mr_ckpt, h->mr_anchor};
+                    h->delay_cur, h->mr_u, h->mr_ckpt, h->mr_anchor, h->innov, h->innov_nis};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -650,6 +651,102 @@ extern "C" int qle_step(qle_batch* h, const double* u, const double* z, const ui
         QLE_TRY(BY_DTYPE(h, launch_step, h, h->tick_u, h->tick_z));
     }
     return advance_tick(h);
+}
+
+// ---- innovation diagnostics and the chi-square gate (k_innov, ekf_innov.hpp) ----
+// The output records are allocated on the first call, so that handles that never ask for them pay nothing.
+static int innov_alloc(qle_batch* h)
+{
+    if (h->innov) return QLE_OK;
+    void *d = nullptr, *n = nullptr;
+    hipError_t e = hipMalloc(&d, (size_t)kDW * (size_t)h->Bp * h->wsz);
+    if (e == hipSuccess) e = hipMalloc(&n, (size_t)h->Bp * h->wsz);
+    if (e != hipSuccess) {
+        if (d) (void)hipFree(d);
+        if (n) (void)hipFree(n);
+        return fail(QLE_ERR_NOMEM, "innovation outputs: %s", hipGetErrorString(e));
+    }
+    h->innov = d; h->innov_nis = n;
+    return QLE_OK;
+}
+// Host copies of the last k_innov launch's outputs (chunked staging; synchronises).  accepted = the mask words of h->tick_z.
+template <typename T>
+static int innov_read_t(qle_batch* h, double* nu, double* S, double* nis, uint8_t* accepted)
+{
+    if (nu) QLE_TRY(unpack_rows<T>(h, h->innov, 6, 6, nu, kDW, 0));
+    if (S) {
+        std::vector<double> sp((size_t)h->B * 21);
+        QLE_TRY(unpack_rows<T>(h, h->innov, 21, 21, sp.data(), kDW, 6));
+        for (int64_t i = 0; i < h->B; ++i)
+            for (int a = 0; a < 6; ++a)
+                for (int b = 0; b < 6; ++b) S[i * 36 + a * 6 + b] = sp[(size_t)i * 21 + (a <= b ? sidx6(a, b) : sidx6(b, a))];
+    }
+    if (nis) QLE_TRY(unpack_rows<T>(h, h->innov_nis, 1, 1, nis, 1, 0));
+    if (accepted) {
+        std::vector<double> m((size_t)h->B);
+        QLE_TRY(unpack_rows<T>(h, h->tick_z, 1, 1, m.data(), kZW, 7));
+        for (int64_t i = 0; i < h->B; ++i) accepted[i] = m[(size_t)i] != 0.0 ? 1 : 0;
+    }
+    return QLE_OK;
+}
+static int check_gate(const qle_batch* h, double chi2_max)
+{
+    if (!(chi2_max > 0.0)) return fail(QLE_ERR_INVALID, "chi2_max must be > 0 (+INFINITY accepts every finite NIS), got %g", chi2_max);
+    if (h->mr) return fail(QLE_ERR_STATE, "the gated calls do not support multirate_ekf: a delayed measurement's innovation belongs to a history entry");
+    if (h->gating) return fail(QLE_ERR_STATE, "the gated calls do not combine with device gating (qle_enable_gating)");
+    return QLE_OK;
+}
+
+extern "C" int qle_innovation(qle_batch* h, const double* z, const uint8_t* mask, double* nu, double* S, double* nis)
+{
+    QLE_TRY(check_handle(h));
+    QLE_TRY(need_state(h));
+    if (!z) return fail(QLE_ERR_INVALID, "z is null");
+    QLE_TRY(innov_alloc(h));
+    QLE_TRY(BY_DTYPE(h, pack_z, h, z, mask, h->tick_z));
+    QLE_TRY(BY_DTYPE(h, launch_innov, h, h->tick_z, false, 0.0));
+    if (!nu && !S && !nis) return QLE_OK;   // outputs stay on the device (asynchronous)
+    QLE_GUARD_BEGIN
+    return BY_DTYPE(h, innov_read_t, h, nu, S, nis, nullptr);
+    QLE_GUARD_END
+}
+
+extern "C" int qle_update_gated(qle_batch* h, const double* z, const uint8_t* mask, double chi2_max, uint8_t* accepted, double* nis)
+{
+    QLE_TRY(check_handle(h));
+    QLE_TRY(need_state(h));
+    if (!z) return fail(QLE_ERR_INVALID, "z is null");
+    QLE_TRY(check_gate(h, chi2_max));
+    QLE_TRY(innov_alloc(h));
+    QLE_TRY(BY_DTYPE(h, pack_z, h, z, mask, h->tick_z));
+    QLE_TRY(BY_DTYPE(h, launch_innov, h, h->tick_z, true, chi2_max));
+    h->hist_dirty = true;
+    QLE_TRY(BY_DTYPE(h, launch_update, h, h->tick_z));
+    if (!accepted && !nis) return QLE_OK;
+    QLE_GUARD_BEGIN
+    return BY_DTYPE(h, innov_read_t, h, nullptr, nullptr, nis, accepted);
+    QLE_GUARD_END
+}
+
+// Three launches, not fused: the predict of qle_step's policy, k_innov as the gate, k_update.
+extern "C" int qle_step_gated(qle_batch* h, const double* u, const double* z, const uint8_t* mask, double chi2_max, uint8_t* accepted,
+                              double* nis)
+{
+    QLE_TRY(check_handle(h));
+    QLE_TRY(need_state(h));
+    if (!u || !z) return fail(QLE_ERR_INVALID, "u and z must be non-null");
+    QLE_TRY(check_gate(h, chi2_max));
+    QLE_TRY(innov_alloc(h));
+    QLE_TRY(BY_DTYPE(h, pack_rows, h, u, kUW, kUW, h->tick_u, kUW, 0));
+    QLE_TRY(BY_DTYPE(h, pack_z, h, z, mask, h->tick_z));
+    QLE_TRY(BY_DTYPE(h, launch_predict, h, h->tick_u));
+    QLE_TRY(BY_DTYPE(h, launch_innov, h, h->tick_z, true, chi2_max));
+    QLE_TRY(BY_DTYPE(h, launch_update, h, h->tick_z));
+    QLE_TRY(advance_tick(h));
+    if (!accepted && !nis) return QLE_OK;
+    QLE_GUARD_BEGIN
+    return BY_DTYPE(h, innov_read_t, h, nullptr, nullptr, nis, accepted);
+    QLE_GUARD_END
 }
 
 // ---- device-side gating: the full single-rate filter_update decision logic ----

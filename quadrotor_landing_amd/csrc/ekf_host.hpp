@@ -104,6 +104,9 @@ struct qle_batch {
     double* delay_cur = nullptr;   // [B] measurement_delay_curr (EKF.hpp:86)
     double t_curr = 0.0, uniform_age = 0.0;
     bool have_stamps = false;
+    // innovation diagnostics (qle_innovation, qle_update_gated, qle_step_gated; ekf_innov.hpp), allocated on first use
+    void* innov = nullptr;         // kDW-word records per filter: nu (6), S packed (21), pad
+    void* innov_nis = nullptr;     // [Bp] NIS per filter
 };
 
 struct qle_inputs {
@@ -281,6 +284,7 @@ int mr_prepare(qle_batch* h);                                                   
 template <typename T> int launch_step_mr(qle_batch* h, const void* u, const void* z);          // tu_misc: k_step_mr
 template <typename T> int launch_update(qle_batch* h, const void* z);                          // tu_misc: k_update
 template <typename T> int run_resident_t(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n);   // tu_misc: k_run_resident
+template <typename T> int launch_innov(qle_batch* h, void* z, bool gate, double chi2_max);                // tu_predict: k_innov
 template <typename T> int launch_predict_sd(qle_batch* h, const void* u, const void* src, void* dst, bool history);   // tu_predict: k_predict
 template <typename T> int launch_step_lane(qle_batch* h, const void* u, const void* z);        // tu_step: k_step
 template <typename T> int launch_quad(qle_batch* h, const void* u, const void* z);             // tu_quad: kw_tick

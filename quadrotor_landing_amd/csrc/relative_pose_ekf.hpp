@@ -74,6 +74,17 @@ public:
     void step(const double* u, const double* z = nullptr, const uint8_t* mask = nullptr) { check(qle_step(h_, u, z, mask)); }
     void enable_gating(bool on) { check(qle_enable_gating(h_, on ? 1 : 0)); }
     void filter_update(const double* u, const double* z, const uint8_t* ready) { check(qle_filter_update(h_, u, z, ready)); }
+    // innovation delta_y, its covariance S and NIS = delta_y^T S^-1 delta_y (relative_pose_EKF.cpp:447-475); the state is unchanged
+    void innovation(const double* z, const uint8_t* mask, double* nu, double* S, double* nis) { check(qle_innovation(h_, z, mask, nu, S, nis)); }
+    // correction_step where NIS <= chi2_max only (16.81 / 22.46: the 0.99 / 0.999 quantiles of chi-square with 6 dof)
+    void update_gated(const double* z, double chi2_max, const uint8_t* mask, uint8_t* accepted, double* nis)
+    {
+        check(qle_update_gated(h_, z, mask, chi2_max, accepted, nis));
+    }
+    void step_gated(const double* u, const double* z, double chi2_max, const uint8_t* mask, uint8_t* accepted, double* nis)
+    {
+        check(qle_step_gated(h_, u, z, mask, chi2_max, accepted, nis));
+    }
     void synchronize() { check(qle_synchronize(h_)); }
 
     qle_params params;

@@ -1,6 +1,7 @@
-// tu_predict.hip -- launcher of k_predict (one lane per filter, predict-only tick)
-// Compiled once per compute dtype (-DQLE_TU_T=float|double); see ekf_host.hpp.
+// tu_predict.hip -- launchers of k_predict (one lane per filter, predict-only tick) and of k_innov (innovation diagnostics and the
+// chi-square gate, ekf_innov.hpp).  Compiled once per compute dtype (-DQLE_TU_T=float|double); see ekf_host.hpp.
 #include "ekf_host.hpp"
+#include "ekf_innov.hpp"
 
 #ifndef QLE_TU_T
 #error "compile with -DQLE_TU_T=float or -DQLE_TU_T=double"
@@ -43,4 +44,28 @@ int launch_predict_sd(qle_batch* h, const void* u, const void* src, void* dst, b
     return QLE_OK;
 }
 
+// k_innov over the handle's state and the tag records `z` (h->tick_z): gate = false writes nu / S into h->innov, gate = true clears the
+// mask word of every record whose NIS is not <= chi2_max; both write NIS into h->innov_nis.  Launched as k_update.
+template <typename T>
+int launch_innov(qle_batch* h, void* z, bool gate, double chi2_max)
+{
+    const DevParams<T>& p = dev<T>(h);
+    const dim3 g = grid_for(h, h->block), b(h->block);
+    const T* st = (const T*)state_cur(h);
+    const T* pfp = (const T*)h->pfp;
+#define QLE_INNOV(D, F, C, G) hipLaunchKernelGGL((k_innov<T, D, F, C, G>), g, b, 0, h->stream, st, (T*)z, h->B, (int32_t)g.x, (int32_t)b.x, pfp, (T*)h->innov, (T*)h->innov_nis, chi2_max, p)
+#define QLE_INNOV_G(D, F, C) do { if (gate) QLE_INNOV(D, F, C, true); else QLE_INNOV(D, F, C, false); } while (0)
+#define QLE_INNOV_C(D, F) do { if (h->compact) QLE_INNOV_G(D, F, true); else QLE_INNOV_G(D, F, false); } while (0)
+#define QLE_INNOV_F(D) do { if (h->pfp_on) QLE_INNOV_C(D, true); else QLE_INNOV_C(D, false); } while (0)
+    if (h->pub.direct_orien_method) QLE_INNOV_F(true);
+    else QLE_INNOV_F(false);
+#undef QLE_INNOV_F
+#undef QLE_INNOV_C
+#undef QLE_INNOV_G
+#undef QLE_INNOV
+    HIP_TRY(hipGetLastError());
+    return QLE_OK;
+}
+
 template int launch_predict_sd<QLE_TU_T>(qle_batch*, const void*, const void*, void*, bool);
+template int launch_innov<QLE_TU_T>(qle_batch*, void*, bool, double);

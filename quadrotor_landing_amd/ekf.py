@@ -181,6 +181,37 @@ class BatchedRelativePoseEKF:
         zz = None if z is None else _f64(z, (self.batch, 7))
         check(lib().qle_step(self._h, _dp(_f64(u, (self.batch, 6))), _dp(zz), None if m is None else m.ctypes.data_as(_pu8)))
 
+    # ---- innovation diagnostics and the chi-square outlier gate
+    def innovation(self, z, mask=None):
+        """(nu [B,6], S [B,6,6], nis [B]) of tag poses z against the current state: the innovation delta_y and its covariance
+        S = G P G^T + R_k of correction_step (relative_pose_EKF.cpp:447-475) and NIS = delta_y^T S^-1 delta_y.  The state is
+        unchanged.  Filters with mask 0 or without state: nu = 0, S = 0, nis = NaN."""
+        B = self.batch
+        m = _u8(mask, (B,))
+        nu = np.empty((B, 6)); S = np.empty((B, 36)); nis = np.empty(B)
+        check(lib().qle_innovation(self._h, _dp(_f64(z, (B, 7))), None if m is None else m.ctypes.data_as(_pu8), _dp(nu), _dp(S), _dp(nis)))
+        return nu, S.reshape(B, 6, 6), nis
+
+    def update_gated(self, z, chi2_max, mask=None):
+        """update(z, mask) on the filters whose NIS <= chi2_max only (16.81 / 22.46: the 0.99 / 0.999 quantiles of chi-square
+        with 6 degrees of freedom).  Returns (accepted [B] bool, nis [B])."""
+        B = self.batch
+        m = _u8(mask, (B,))
+        acc = np.zeros(B, np.uint8); nis = np.empty(B)
+        check(lib().qle_update_gated(self._h, _dp(_f64(z, (B, 7))), None if m is None else m.ctypes.data_as(_pu8), float(chi2_max),
+                                     acc.ctypes.data_as(_pu8), _dp(nis)))
+        return acc.astype(bool), nis
+
+    def step_gated(self, u, z, chi2_max, mask=None):
+        """step(u, z, mask) with the same gate between predict and correct (three launches, not the fused tick).
+        Returns (accepted [B] bool, nis [B])."""
+        B = self.batch
+        m = _u8(mask, (B,))
+        acc = np.zeros(B, np.uint8); nis = np.empty(B)
+        check(lib().qle_step_gated(self._h, _dp(_f64(u, (B, 6))), _dp(_f64(z, (B, 7))), None if m is None else m.ctypes.data_as(_pu8),
+                                   float(chi2_max), acc.ctypes.data_as(_pu8), _dp(nis)))
+        return acc.astype(bool), nis
+
     # ---- filter_update with the decision logic on the device (relative_pose_EKF.cpp:147-186)
     def enable_gating(self, on=True):
         check(lib().qle_enable_gating(self._h, int(bool(on))))
