@@ -239,18 +239,6 @@ static void choose_cache_policy(qle_batch* h)
         const int k64 = (int)std::lround(64.0 * 216.0 / std::max(state_mib, 1.0));
         h->split = -std::min(63, std::max(1, k64));
         if (state_mib > 64.0 * 240.0) h->nt = 2;       // even 1/64 of it would not fit: stream everything
-        // QLE_CHUNK=n (experiments; profiles/r04_tuning.md section 4): the lane-per-filter single-rate ticks are launched n filters at a time and
-        // the cache policy is the one of an n-filter state
-        h->chunk = 0;
-        if (const char* s = std::getenv("QLE_CHUNK")) {
-            const int64_t c = std::atoll(s);
-            if (c >= 256 && c % 256 == 0 && c < h->B) {
-                h->chunk = c;
-                const double chunk_mib = (double)(h->compact ? kXW + kPWc : kSW) * (double)c * (double)h->wsz / (1024.0 * 1024.0);
-                h->nt = chunk_mib <= 48.0 ? 1 : (chunk_mib <= 300.0 ? 0 : 3);
-                h->nt_refresh = chunk_mib <= 40.0 ? 128 : 0;
-            }
-        }
         if (const char* s = std::getenv("QLE_NT")) h->nt = std::min(3, std::max(0, std::atoi(s)));
         if (const char* s = std::getenv("QLE_SPLIT")) h->split = std::atoi(s);
     }
@@ -300,8 +288,8 @@ extern "C" int qle_create(qle_batch** out, int64_t batch, int32_t dtype, int32_t
     if (const char* s = std::getenv("QLE_QUAD")) { h->quad = std::atoi(s) & 7; h->quad_auto = false; }
     // Multirate history: a state checkpoint every mr_k ticks: a predict tick streams 136/k extra words, a correction replays
     // (k-1)/2 extra predictions on average.  Measured on cfg 3 with a 12-tick camera latency (profiles/r02_tuning.md): k = 4 / 8 / 16
-    // -> predict tick 11.7 / 10.9 / 10.4 us, whole schedule 16.1 / 15.1 / 15.1 us per tick; 16 ships (history 0.6 GB).
-    if (const char* s = std::getenv("QLE_MR_K")) h->mr_k = std::min(64, std::max(1, std::atoi(s)));
+    // -> predict tick 11.7 / 10.9 / 10.4 us, whole schedule 16.1 / 15.1 / 15.1 us per tick; with the extra checkpoint at the expected
+    // entry (profiles/r03_tuning.md) k = 8 / 16 / 32 / 64: 14.55 / 13.83 / 13.47 / 13.32 us: 32 ships (qle_batch::mr_k).
     if (const char* s = std::getenv("QLE_TICK_REBASE")) {
         const long long v = std::atoll(s);
         if (v >= 16) h->rebase_at = v;

@@ -1,7 +1,7 @@
 // ekf_host.hpp -- host side shared by the translation units of libqle_ekf.so: the handle, its helpers and the
-// declarations of the kernel launchers.  The kernels are instantiated in separate translation units
-// (tu_predict / tu_step / tu_quad / tu_misc .hip, each compiled once per compute dtype) so that the library builds
-// in parallel; ekf_capi.hip holds the C-ABI.  There is deliberately no CPU compute path.
+// kernel launchers.  The kernels are instantiated in separate translation units (tu_predict / tu_step / tu_quad /
+// tu_misc / tu_compact .hip, each compiled once per compute dtype) so that the library builds in parallel; ekf_capi.hip
+// holds the C-ABI.  There is deliberately no CPU compute path.
 #pragma once
 
 #include "../../include/qle_ekf.h"
@@ -16,6 +16,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ekf_kernels.hpp"
@@ -54,7 +55,6 @@ struct qle_batch {
     int32_t split = 0;        // nt == 3: which workgroups keep their tiles cached (cached_workgroup() in ekf_kernels.hpp)
     int32_t nt_refresh = 0;   // > 0: nt == 1 and the state is <= 40 MiB: non-temporal stores, cached-store tick every nt_refresh ticks
     int32_t nt = 0;        // cache policy of the hot kernels' state accesses: 0 cached, 1 L2-sized scheme (effective_nt), 2 non-temporal, 3 split
-    int64_t chunk = 0;     // > 0: the lane-per-filter single-rate ticks are launched in chunks of this many filters (choose_cache_policy)
     bool quad_auto = true; // quad follows the rules of qle_create / qle_set_params (false: QLE_QUAD given)
     int32_t quad = 0;      // workgroup-cooperative tick kernel (ekf_quad_kernels.hpp): bit 0 ticks with tag poses, bit 1 predict-only ticks
     size_t wsz = 4;
@@ -107,6 +107,9 @@ struct qle_batch {
     // innovation diagnostics (qle_innovation, qle_update_gated, qle_step_gated; ekf_innov.hpp), allocated on first use
     void* innov = nullptr;         // kDW-word records per filter: nu (6), S packed (21), pad
     void* innov_nis = nullptr;     // [Bp] NIS per filter
+    // kernels whose dynamic-LDS limit this handle has raised on its device (launch() below); the oldest entry makes room
+    const void* lds_raised[8] = {};
+    int32_t lds_next = 0;
 };
 
 struct qle_inputs {
@@ -147,15 +150,6 @@ template <> const DevParams<float>& dev<float>(const qle_batch* h) { return h->p
 template <> const DevParams<double>& dev<double>(const qle_batch* h) { return h->pd; }
 
 static inline dim3 grid_for(const qle_batch* h, int block) { return dim3((unsigned)((h->B + block - 1) / block)); }
-// One tick as a sequence of launches over [i0, end): the whole batch at once, or h->chunk filters at a time.
-template <typename F> static inline void for_chunks(const qle_batch* h, int block, F&& launch)
-{
-    const int64_t step = h->chunk > 0 ? h->chunk : h->B;
-    for (int64_t i0 = 0; i0 < h->B; i0 += step) {
-        const int64_t end = std::min(h->B, i0 + step);
-        launch(dim3((unsigned)((end - i0 + block - 1) / block)), i0, end);
-    }
-}
 
 static inline size_t slot_bytes(const qle_batch* h) { return (size_t)kSW * (size_t)h->Bp * h->wsz; }
 // the state: one record array, updated in place by every tick
@@ -268,28 +262,146 @@ static inline void mr_schedule_extra(qle_batch* h)
 // fp64 kernels that keep the covariance split between the LDS and registers (ekf_split.hpp) are launched with 37.5 KiB of dynamic LDS per
 // wave: 150 KiB for a 256-thread workgroup, more than the 64 KiB a launch gets without asking.
 template <typename T> static inline size_t split_lds(const qle_batch* h) { return sizeof(T) == 8 ? (size_t)(h->block / kTile) * kMrLdsPerWave : 0; }
-#define QLE_ASK_LDS(KERNEL, BYTES)                                                                                                    \
-    do {                                                                                                                               \
-        if ((BYTES) > 65536) {                                                                                                         \
-            static bool asked = false;   /* per call site = per instantiation; the attribute is a property of the kernel */             \
-            if (!asked) {                                                                                                              \
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES))); \
-                asked = true;                                                                                                          \
-            }                                                                                                                          \
-        }                                                                                                                              \
-    } while (0)
 
-// ---- kernel launchers, defined and explicitly instantiated for float and double in the tu_*.hip files ----
-int mr_prepare(qle_batch* h);                                                                  // tu_misc
+// ------------------------------------------------------------------ kernel selection and launch
+// The launchers turn runtime state into template arguments with these: f receives the std::integral_constant of the listed value that
+// equals the runtime one, and a generic lambda passes it on as a template argument.  A list names exactly the variants a launcher
+// instantiates; a value outside it is an error, never another variant.
+template <typename F> static inline int with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// ON = false: this instantiation has no `true` variant; b is ignored and f receives false
+template <bool ON, typename F> static inline int with_bool_if(bool b, F&& f)
+{
+    if constexpr (ON) return with_bool(b, f);
+    else return f(std::false_type{});
+}
+template <int... Vs, typename F> static inline int with_int(int v, F&& f)
+{
+    int rc = QLE_OK;
+    if (((v == Vs && (rc = f(std::integral_constant<int, Vs>{}), true)) || ...)) return rc;
+    return fail(QLE_ERR_INVALID, "internal: no kernel variant for the value %d", v);
+}
+
+// One kernel launch on the handle's stream.  More dynamic LDS than the 64 KiB default needs the kernel's limit raised first.  The limit
+// belongs to the kernel on one device and is shared by every handle there, so it is always raised to the largest request any handle
+// makes (a 256-thread split workgroup; a smaller value could lower another handle's limit), and each handle lists the kernels it raised
+// it for.  A handle has one device (made current by check_handle) and one host thread: the list needs no lock, and a launch of a listed
+// kernel makes no extra runtime call.
+constexpr size_t kMaxSplitLds = (size_t)(kBlock / kTile) * kMrLdsPerWave;
+template <typename K, typename... Args>
+static inline int launch(qle_batch* h, K* kernel, dim3 grid, dim3 block, size_t lds, const Args&... args)
+{
+    if (lds > 65536) {
+        const void* k = reinterpret_cast<const void*>(kernel);
+        constexpr int n = (int)(sizeof(h->lds_raised) / sizeof(h->lds_raised[0]));
+        if (std::find(h->lds_raised, h->lds_raised + n, k) == h->lds_raised + n) {
+            HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxSplitLds));
+            h->lds_raised[h->lds_next++ % n] = k;
+        }
+    }
+    hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, args...);
+    HIP_TRY(hipGetLastError());
+    return QLE_OK;
+}
+
+// ---- kernel launchers, explicitly instantiated for float and double in the tu_*.hip files ----
+int mr_prepare(qle_batch* h);                                                                  // ekf_capi
 template <typename T> int launch_step_mr(qle_batch* h, const void* u, const void* z);          // tu_misc: k_step_mr
-template <typename T> int launch_update(qle_batch* h, const void* z);                          // tu_misc: k_update
-template <typename T> int run_resident_t(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n);   // tu_misc: k_run_resident
-template <typename T> int launch_innov(qle_batch* h, void* z, bool gate, double chi2_max);                // tu_predict: k_innov
-template <typename T> int launch_predict_sd(qle_batch* h, const void* u, const void* src, void* dst, bool history);   // tu_predict: k_predict
-template <typename T> int launch_step_lane(qle_batch* h, const void* u, const void* z);        // tu_step: k_step
+template <typename T> int launch_innov(qle_batch* h, void* z, bool gate, double chi2_max);     // tu_predict: k_innov
 template <typename T> int launch_quad(qle_batch* h, const void* u, const void* z);             // tu_quad: kw_tick
-// tu_compact: the same lane-per-filter kernels instantiated for compact records (h->compact)
-template <typename T> int launch_predict_compact(qle_batch* h, const void* u, const void* src, void* dst);
-template <typename T> int launch_step_compact(qle_batch* h, const void* u, const void* z);
-template <typename T> int launch_update_compact(qle_batch* h, const void* z);
-template <typename T> int run_resident_compact(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n);
+// The lane-per-filter kernels on full records (COMPACT = false: tu_predict, tu_step, tu_misc) or compact ones (COMPACT = true: tu_compact).
+template <typename T, bool COMPACT> int predict_lanes(qle_batch* h, const void* u, const void* src, void* dst, bool history);   // k_predict
+template <typename T, bool COMPACT> int step_lanes(qle_batch* h, const void* u, const void* z);                                // k_step
+template <typename T, bool COMPACT> int update_lanes(qle_batch* h, const void* z);                                             // k_update
+template <typename T, bool COMPACT> int resident_lanes(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n);             // k_run_resident
+// ... for the handle's record layout
+template <typename T> static inline int launch_predict_sd(qle_batch* h, const void* u, const void* src, void* dst, bool history)
+{
+    return h->compact ? predict_lanes<T, true>(h, u, src, dst, history) : predict_lanes<T, false>(h, u, src, dst, history);
+}
+template <typename T> static inline int launch_step_lane(qle_batch* h, const void* u, const void* z)
+{
+    return h->compact ? step_lanes<T, true>(h, u, z) : step_lanes<T, false>(h, u, z);
+}
+template <typename T> static inline int launch_update(qle_batch* h, const void* z)
+{
+    return h->compact ? update_lanes<T, true>(h, z) : update_lanes<T, false>(h, z);
+}
+template <typename T> static inline int run_resident_t(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n)
+{
+    return h->compact ? resident_lanes<T, true>(h, in, t0, n) : resident_lanes<T, false>(h, in, t0, n);
+}
+
+#ifdef QLE_TU_T
+// The bodies of the lane-per-filter launchers, seen by the tu_*.hip units only: each unit instantiates its side, and ekf_capi.hip
+// (which sees the declarations above) instantiates no kernel.
+
+// prediction_step from `src` into `dst`; history: the tick also appends to the multirate history (full records only: compact records
+// never carry it, qle_set_params).
+template <typename T, bool COMPACT>
+int predict_lanes(qle_batch* h, const void* u, const void* src, void* dst, bool history)
+{
+    const DevParams<T>& p = dev<T>(h);
+    const dim3 g = grid_for(h, h->block), b(h->block);
+    T* acc = h->aux ? (T*)h->aux_accel : (T*)nullptr;
+    history = history && !COMPACT;
+    // multirate history of this tick: the IMU sample's ring slot and, on checkpoint ticks, the checkpoint slot
+    T* hu = history ? (T*)mr_u_slot_host(h, h->tick) : (T*)nullptr;
+    bool extra_ck = false;
+    T* hc = history ? (T*)mr_ck_for_predict(h, h->tick, &extra_ck) : (T*)nullptr;
+    // the extra checkpoint stays in the Infinity Cache when it fits there next to the state (cached stores), else it is streamed
+    const int32_t ck_cached = extra_ck && 2 * slot_bytes(h) <= ((size_t)200 << 20) ? 1 : 0;
+    // "loads first" (predict_tick): the fp32 tick of a batch that gives every SIMD at most one wave
+    return with_bool(h->pfp_on, [&](auto F) {
+    return with_int<0, 1, 2, 3>(effective_nt(h), [&](auto N) {
+    return with_bool_if<!COMPACT>(history, [&](auto M) {
+    return with_bool_if<sizeof(T) == 4 && !COMPACT>(h->loads_first, [&](auto L) {
+        return launch(h, k_predict<T, F, N, M, COMPACT, L>, g, b, 0, (const T*)src, (T*)dst, (const T*)u, h->B, (int64_t)0, (int32_t)g.x,
+                      (int32_t)b.x, h->split, ck_cached, (const T*)h->pfp, acc, hu, hc, p);
+    }); }); }); });
+}
+
+template <typename T, bool COMPACT>
+int step_lanes(qle_batch* h, const void* u, const void* z)
+{
+    const DevParams<T>& p = dev<T>(h);
+    const GateParams gp = make_gate(h);
+    const dim3 g = grid_for(h, h->block), b(h->block);
+    T *st = (T*)state_cur(h), *acc = h->aux ? (T*)h->aux_accel : (T*)nullptr, *obs = h->aux ? (T*)h->aux_obs : (T*)nullptr;
+    return with_bool(h->pub.direct_orien_method, [&](auto D) {
+    return with_bool(h->gating, [&](auto G) {
+    return with_bool(h->pfp_on, [&](auto F) {
+    return with_int<0, 1, 2, 3>(effective_nt(h), [&](auto N) {
+        return launch(h, k_step<T, D, F, G, N, COMPACT>, g, b, 0, st, (const T*)u, (const T*)z, h->B, (int64_t)0, (int32_t)g.x, (int32_t)b.x,
+                      h->split, (const T*)h->pfp, acc, obs, h->last_corr, h->flags, p, gp);
+    }); }); }); });
+}
+
+template <typename T, bool COMPACT>
+int update_lanes(qle_batch* h, const void* z)
+{
+    const DevParams<T>& p = dev<T>(h);
+    const dim3 g = grid_for(h, h->block), b(h->block);
+    T *st = (T*)state_cur(h), *obs = h->aux ? (T*)h->aux_obs : (T*)nullptr;
+    return with_bool(h->pub.direct_orien_method, [&](auto D) {
+    return with_bool(h->pfp_on, [&](auto F) {
+        return launch(h, k_update<T, D, F, COMPACT>, g, b, split_lds<T>(h), st, (const T*)z, h->B, (int32_t)g.x, (int32_t)b.x, (const T*)h->pfp,
+                      obs, p);
+    }); });
+}
+
+// On-chip-resident variant: ONE launch advances every filter by n ticks with x and P held in
+// registers; HBM traffic is the state once plus the inputs.  Not the unit of work of the headline
+// metric (one launch per tick); reported separately.
+template <typename T, bool COMPACT>
+int resident_lanes(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n)
+{
+    const DevParams<T>& p = dev<T>(h);
+    const dim3 g = grid_for(h, h->block), b(h->block);
+    const int64_t pu = (int64_t)(in->pitch_u / h->wsz), pz = (int64_t)(in->pitch_z / h->wsz);
+    return with_bool(h->pub.direct_orien_method, [&](auto D) {
+    return with_bool(h->pfp_on, [&](auto F) {
+        return launch(h, k_run_resident<T, D, F, COMPACT>, g, b, split_lds<T>(h), p, (T*)state_cur(h), (const T*)in->u, (const T*)in->z,
+                      (const int32_t*)in->d_slot, pu, pz, in->T, t0, n, (const T*)h->pfp, h->B);
+    }); });
+}
+#endif

@@ -34,15 +34,6 @@ namespace qle {
 #ifndef QLE_RING_POLICY
 #define QLE_RING_POLICY 2
 #endif
-// How many replayed ticks ahead k_step_mr requests its stored IMU samples (1..4).  Measured at 1 / 2 / 3 / 4 (profiles/r04_tuning.md section 8):
-// k_step_mr<float> 40.2 / 41.6 / 40.5 / 41.6 us, <double> 89.6 / 90.9 / 91.4 / 91.8 -- one is enough, the anchor's stores do not hold the
-// replay up.
-#ifndef QLE_MR_PREFETCH_F32
-#define QLE_MR_PREFETCH_F32 1
-#endif
-#ifndef QLE_MR_PREFETCH_F64
-#define QLE_MR_PREFETCH_F64 1
-#endif
 constexpr int kBlock = 256;
 constexpr int kTile = 64;   // filters per tile = wavefront size
 
@@ -468,7 +459,7 @@ __global__ __launch_bounds__(kBlock, PredictWaves<T>::value) void k_predict(cons
     // hidden arguments are not among the preloaded ones) instead of fetching them from the kernel-argument segment -- a memory round
     // trip in front of every launch's first load.  The parameter block, needed when the first data arrive, comes last.
     QLE_ARGS_EARLY(src, dst, us, B, i0, grid_x, block_x);
-    const int64_t i = i0 + batch_block((unsigned)grid_x) * block_x + threadIdx.x;   // i0: first filter of this launch (a tick may be launched in chunks)
+    const int64_t i = i0 + batch_block((unsigned)grid_x) * block_x + threadIdx.x;   // i0: first filter of this launch (the launchers pass 0)
     if (i >= B) return;
     if (NT == 3) {
         if (cached_workgroup(split)) predict_tick<T, PFP, 0, MR, COMPACT, LF>(p, src, dst, us, pfp, aux_accel, hist_u, hist_ck, ck_cached != 0, i);
@@ -931,20 +922,16 @@ __global__ __launch_bounds__(kBlock) void k_step_mr(T* cur, const T* __restrict_
     // fp32, regular cadence: every lane's chain starts AT its measurement's entry (the extra checkpoint).  The correction then runs on the
     // loaded triangle directly -- its scalar chains (innovation, R_k) under the tail of the 36 MB load, no pack / unpack round trip through
     // the register blocks in front of it -- and the loop below finds nothing left to correct (wave-uniform choice).
-    // The IMU samples of the next kQ replayed ticks are requested ahead (wave-uniform slot addresses), the first kQ in front of the
-    // correction.  kQ = 1 ships: one step of arithmetic (~1.8 us) covers the latency of the ring, which was streamed to HBM; deeper queues
-    // (the idea: a sample requested behind the 36 / 72 MB of anchor stores is not delivered before they have drained) measured no gain, and
-    // requesting the whole window up front (LDS-DMA, profiles/r03_tuning.md) made the prologue 15 000 cycles longer.
+    // The IMU sample of the next replayed tick is requested one tick ahead (wave-uniform slot addresses), the first in front of the
+    // correction: one step of arithmetic (~1.8 us) covers the latency of the ring, which was streamed to HBM.  Deeper queues (the idea: a
+    // sample requested behind the 36 / 72 MB of anchor stores is not delivered before they have drained) measured no gain at 2 / 3 / 4
+    // ticks ahead (profiles/r04_tuning.md section 8), and requesting the whole window up front (LDS-DMA, profiles/r03_tuning.md) made the
+    // prologue 15 000 cycles longer.
     // A sample index beyond the current tick has no request; the current tick's own sample comes from `us` (it is asked for again here so
     // that it is not carried in registers through the whole replay).
-    constexpr int kQ = sizeof(T) == 4 ? QLE_MR_PREFETCH_F32 : QLE_MR_PREFETCH_F64;
-    static_assert(kQ >= 1 && kQ <= 4, "the sample queue is four named register arrays");
-    T un0[kUW], un1[kUW], un2[kUW], un3[kUW];   // separate arrays: a [kQ][kHW] array was left in scratch by the backend
+    T un0[kUW];
     auto request_sample = [&](int32_t ts, T (&dst)[kUW]) { mr_request_sample<T>(m, uring, us, i, ts, dst); };   // ts is wave-uniform
     request_sample(t_lo + 1, un0);
-    if constexpr (kQ > 1) request_sample(t_lo + 2, un1);
-    if constexpr (kQ > 2) request_sample(t_lo + 3, un2);
-    if constexpr (kQ > 3) request_sample(t_lo + 4, un3);
     bool early = false;
     if (sp != cur) load_rec<T, kSW, 0, kXW>(sp, i, x);
     if constexpr (sizeof(T) == 4) {
@@ -986,16 +973,7 @@ __global__ __launch_bounds__(kBlock) void k_step_mr(T* cur, const T* __restrict_
 #pragma unroll
         for (int k = 0; k < kUW; ++k) u6[k] = un0[k];
         QLE_STAMP(8 + 2 * dbg_j, u6[0] + u6[5]);
-#pragma unroll
-        for (int k = 0; k < kUW; ++k) {
-            if constexpr (kQ > 1) un0[k] = un1[k];
-            if constexpr (kQ > 2) un1[k] = un2[k];
-            if constexpr (kQ > 3) un2[k] = un3[k];
-        }
-        if constexpr (kQ == 1) request_sample(t + 1, un0);
-        else if constexpr (kQ == 2) request_sample(t + 2, un1);
-        else if constexpr (kQ == 3) request_sample(t + 3, un2);
-        else request_sample(t + 4, un3);
+        request_sample(t + 1, un0);
         if (valid && t > start) {
             if constexpr (sizeof(T) == 8 && PFP) load_noise<T, PFP>(p, pfp, i, nz);   // fp64: 24 values read again (L2) rather than 48 registers held through the loop
             S.predict(p, nz, x, u6, accel);

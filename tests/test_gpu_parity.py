@@ -14,6 +14,8 @@ regenerated with QLE_TOL_RECORD -- none is more than ~10x its measurement):
       the correction divides by the pivots of S, cond(S) more digits go); free runs of 40-1000 ticks: 2e-5 ... 6e-5 (state), 5e-5
       ... 4e-4 (covariance), each about 10x what that run measures.
 """
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -526,6 +528,41 @@ def test_launch_rules_do_not_change_results_large_ragged_batch(monkeypatch, kern
         np.testing.assert_array_equal(xo, xs); np.testing.assert_array_equal(Po, Ps)
         for k in env:
             monkeypatch.delenv(k)
+
+
+def test_split_lds_limit_is_raised_for_every_handle(monkeypatch):
+    """fp64 k_update keeps the covariance split between registers and 37.5 KiB of dynamic LDS per wave (ekf_split.hpp), more than a
+    launch gets without raising the kernel's limit: 75 KiB for a 128-thread workgroup, 150 KiB for the default 256 threads at 65 536
+    filters.  Each handle raises the limit on its own device, and never lowers another's: in one process a 128-thread handle, then a
+    default one, then each once more succeed and agree bit for bit -- and so does a default handle on a second device, if there is one."""
+    po, pq = both(update_freq=100.0, **HW)
+    rng = np.random.default_rng(4100)
+    B = 65536
+    x, P = rand_states(rng, B, 15, cov_scale=0.3)
+    z = meas_near(rng, po, x)
+    mask = (rng.uniform(size=B) < 0.7).astype(np.uint8)
+
+    def update(block, device=0):
+        if block is not None:
+            monkeypatch.setenv("QLE_BLOCK", str(block))
+        e = qla.BatchedRelativePoseEKF(B, "f64", device=device, params=pq)
+        monkeypatch.delenv("QLE_BLOCK", raising=False)
+        assert e.policy()["block"] == (block or 256)
+        e.set_state(x, P)
+        e.update(z, mask)
+        out = e.get_state()
+        e.close()
+        return out
+
+    x128, P128 = update(128)
+    assert np.abs(x128 - x).max() > 1e-3                  # the correction did something
+    others = [update(None), update(128), update(None)]
+    n = ctypes.c_int32(0)
+    assert qla.lib().qle_device_count(ctypes.byref(n)) == 0
+    if n.value >= 2:
+        others.append(update(None, device=1))
+    for xo, Po in others:
+        np.testing.assert_array_equal(xo, x128); np.testing.assert_array_equal(Po, P128)
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
