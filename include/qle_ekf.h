@@ -332,6 +332,14 @@ int qle_get_policy(const qle_batch *h, qle_policy *out);
  * kind 0 = predict tick, 1 = fused predict+update tick, 2 = stand-alone update. */
 int64_t qle_algorithmic_bytes(const qle_batch *h, int32_t kind);
 
+/* ---- launch census (diagnostics) ------------------------------------------- */
+/* Process-wide list of the distinct kernels launched since qle_launch_census_begin (all handles, all host threads).
+ * qle_launch_census_end stops the census and writes the list -- the kernels' mangled names, sorted, each followed by '\n', then a
+ * NUL -- into names when cap bytes suffice (names may be NULL); *needed receives the bytes the list takes.  The list is kept
+ * until the next begin, so end may be called again with a larger buffer.  Off, the census costs one relaxed atomic load per launch. */
+int qle_launch_census_begin(void);
+int qle_launch_census_end(char *names, int64_t cap, int64_t *needed);
+
 #ifdef __cplusplus
 }
 #endif

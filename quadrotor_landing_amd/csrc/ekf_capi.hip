@@ -7,6 +7,10 @@
 #include "ekf_innov.hpp"
 #include "synth_kernels.hpp"
 
+#include <dlfcn.h>
+
+#include <mutex>
+
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
 
@@ -22,6 +26,62 @@ int qle_fail(int code, const char* fmt, ...)
 }
 
 extern "C" const char* qle_last_error(void) { return g_err.c_str(); }
+
+// ------------------------------------------------------------------ launch census
+// The distinct kernels that launch() (ekf_host.hpp) has launched since qle_launch_census_begin, process-wide: a process may drive one
+// handle per device from several host threads, so the list is guarded by a mutex.  While the census is off, launch()
+// pays one relaxed atomic load.
+std::atomic<bool> g_census_on{false};
+static std::mutex g_census_mu;
+static std::vector<const void*> g_census;
+
+void census_record(const void* kernel)
+{
+    std::lock_guard<std::mutex> lock(g_census_mu);
+    if (g_census_on.load(std::memory_order_relaxed) && std::find(g_census.begin(), g_census.end(), kernel) == g_census.end())
+        g_census.push_back(kernel);
+}
+
+extern "C" int qle_launch_census_begin(void)
+{
+    QLE_GUARD_BEGIN
+    std::lock_guard<std::mutex> lock(g_census_mu);
+    g_census.clear();
+    g_census_on.store(true, std::memory_order_relaxed);
+    return QLE_OK;
+    QLE_GUARD_END
+}
+
+// The host handle of a kernel is an exported symbol of this library whose name is the device kernel's mangled name.
+static const char* kernel_name(const void* kernel)
+{
+    Dl_info info;
+    if (dladdr(kernel, &info) && info.dli_sname && info.dli_saddr == kernel) return info.dli_sname;
+    return hipKernelNameRefByPtr(kernel, nullptr);
+}
+
+extern "C" int qle_launch_census_end(char* names, int64_t cap, int64_t* needed)
+{
+    QLE_GUARD_BEGIN
+    std::lock_guard<std::mutex> lock(g_census_mu);
+    g_census_on.store(false, std::memory_order_relaxed);
+    std::vector<std::string> list;
+    for (const void* k : g_census) {
+        const char* n = kernel_name(k);
+        if (!n) return fail(QLE_ERR_INVALID, "launch census: no symbol name for the kernel at %p", k);
+        list.emplace_back(n);
+    }
+    std::sort(list.begin(), list.end());
+    std::string out;
+    for (const std::string& n : list) out += n + "\n";
+    if (needed) *needed = (int64_t)out.size() + 1;
+    if (names) {
+        if (cap < (int64_t)out.size() + 1) return fail(QLE_ERR_INVALID, "launch census: %lld bytes needed, %lld given", (long long)out.size() + 1, (long long)cap);
+        std::memcpy(names, out.c_str(), out.size() + 1);
+    }
+    return QLE_OK;
+    QLE_GUARD_END
+}
 extern "C" const char* qle_version(void) { return "quadrotor_landing_amd 0.1 (gfx950)"; }
 
 extern "C" int qle_device_count(int32_t* count)
@@ -185,9 +245,8 @@ extern "C" int qle_set_params(qle_batch* h, const qle_params* p)
     bool compact = !p->est_bias && !mr && h->quad == 0;
     if (const char* s = std::getenv("QLE_COMPACT")) compact = std::atoi(s) != 0 && !p->est_bias && !mr;
     if (compact != h->compact && h->state_set) {   // a live state changes layout with the parameters
-        if (h->dtype == QLE_F32) hipLaunchKernelGGL((k_relayout_P<float>), grid_for(h, 256), dim3(256), 0, h->stream, (float*)h->ring, (int)h->compact, (int)compact, h->B);
-        else hipLaunchKernelGGL((k_relayout_P<double>), grid_for(h, 256), dim3(256), 0, h->stream, (double*)h->ring, (int)h->compact, (int)compact, h->B);
-        HIP_TRY(hipGetLastError());
+        if (h->dtype == QLE_F32) QLE_TRY(launch(h, k_relayout_P<float>, grid_for(h, 256), dim3(256), 0, (float*)h->ring, (int)h->compact, (int)compact, h->B));
+        else QLE_TRY(launch(h, k_relayout_P<double>, grid_for(h, 256), dim3(256), 0, (double*)h->ring, (int)h->compact, (int)compact, h->B));
     }
     if (compact != h->compact) { h->compact = compact; choose_cache_policy(h); }
     h->pub = *p;
@@ -395,9 +454,7 @@ static int pack_rows(qle_batch* h, const double* host, int stride, int W, void* 
     for (int64_t i0 = 0; i0 < h->B; i0 += chunk) {
         const int64_t n = std::min(chunk, h->B - i0);
         HIP_TRY(hipMemcpyAsync(h->stage, host + i0 * stride, (size_t)n * stride * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL((k_pack_off<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->stage, stride, W,
-                           (T*)dst, WT, w0, i0, n);
-        HIP_TRY(hipGetLastError());
+        QLE_TRY(launch(h, k_pack_off<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const double*)h->stage, stride, W, (T*)dst, WT, w0, i0, n));
         HIP_TRY(hipStreamSynchronize(h->stream));  // staging buffer is reused by the next chunk
     }
     return QLE_OK;
@@ -408,9 +465,7 @@ static int unpack_rows(qle_batch* h, const void* src, int stride, int W, double*
     const int64_t chunk = std::min<int64_t>(kStageFilters, kStageDoubles / std::max(stride, 1));
     for (int64_t i0 = 0; i0 < h->B; i0 += chunk) {
         const int64_t n = std::min(chunk, h->B - i0);
-        hipLaunchKernelGGL((k_unpack_off<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const T*)src, stride, W, h->stage,
-                           WT, w0, i0, n);
-        HIP_TRY(hipGetLastError());
+        QLE_TRY(launch(h, k_unpack_off<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const T*)src, stride, W, h->stage, WT, w0, i0, n));
         HIP_TRY(hipMemcpyAsync(host + i0 * stride, h->stage, (size_t)n * stride * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
@@ -423,9 +478,8 @@ static int pack_z(qle_batch* h, const double* z, const uint8_t* mask, void* dst)
         const int64_t n = std::min(kStageFilters, h->B - i0);
         if (z) HIP_TRY(hipMemcpyAsync(h->stage, z + i0 * 7, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice, h->stream));
         if (mask) HIP_TRY(hipMemcpyAsync(h->stage_mask, mask + i0, (size_t)n, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL((k_pack_z_off<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, z ? (const double*)h->stage : nullptr,
-                           mask ? (const uint8_t*)h->stage_mask : nullptr, (T*)dst, i0, n);
-        HIP_TRY(hipGetLastError());
+        QLE_TRY(launch(h, k_pack_z_off<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, z ? (const double*)h->stage : nullptr,
+                       mask ? (const uint8_t*)h->stage_mask : nullptr, (T*)dst, i0, n));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return QLE_OK;
@@ -437,9 +491,7 @@ static int pack_P(qle_batch* h, const double* P, void* dst)
     for (int64_t i0 = 0; i0 < h->B; i0 += kStageFilters) {
         const int64_t m = std::min(kStageFilters, h->B - i0);
         HIP_TRY(hipMemcpyAsync(h->stage, P + i0 * n * n, (size_t)m * n * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL((k_pack_P_off<T>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->stage, n, (T*)dst,
-                           i0, m, (int)h->compact);
-        HIP_TRY(hipGetLastError());
+        QLE_TRY(launch(h, k_pack_P_off<T>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (const double*)h->stage, n, (T*)dst, i0, m, (int)h->compact));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return QLE_OK;
@@ -450,8 +502,7 @@ static int unpack_P(qle_batch* h, const void* src, double* P)
     const int n = h->der.num_states;
     for (int64_t i0 = 0; i0 < h->B; i0 += kStageFilters) {
         const int64_t m = std::min(kStageFilters, h->B - i0);
-        hipLaunchKernelGGL((k_unpack_P_off<T>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, (const T*)src, n, h->stage, i0, m, (int)h->compact);
-        HIP_TRY(hipGetLastError());
+        QLE_TRY(launch(h, k_unpack_P_off<T>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (const T*)src, n, h->stage, i0, m, (int)h->compact));
         HIP_TRY(hipMemcpyAsync(P + i0 * n * n, h->stage, (size_t)m * n * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
@@ -466,8 +517,7 @@ extern "C" int qle_set_state(qle_batch* h, const double* x, const double* P)
     QLE_TRY(BY_DTYPE(h, pack_rows, h, x, kXW, kXW, state_cur(h), kSW, 0));
     QLE_TRY(BY_DTYPE(h, pack_P, h, P, state_cur(h)));
     if (!h->state_set && h->last_corr) {   // first state of the handle: upds_since_correction = 0 now (EKF.cpp:77)
-        hipLaunchKernelGGL(k_fill_i32<int32_t>, grid_for(h, 256), dim3(256), 0, h->stream, h->last_corr, (int32_t)(h->tick - 1), h->B);
-        HIP_TRY(hipGetLastError());
+        QLE_TRY(launch(h, k_fill_i32<int32_t>, grid_for(h, 256), dim3(256), 0, h->last_corr, (int32_t)(h->tick - 1), h->B));
     }
     h->state_set = true;
     h->hist_dirty = true;
@@ -547,8 +597,7 @@ extern "C" int qle_get_aux(qle_batch* h, double* accel_rel, double* obs)
 int mr_prepare(qle_batch* h)
 {
     if (h->mr && h->hist_dirty) {   // every filter's history = the single entry "state now": anchor <- state, hist_first = tick-1
-        hipLaunchKernelGGL(k_fill_i32<int32_t>, grid_for(h, 256), dim3(256), 0, h->stream, h->hist_first, (int32_t)(h->tick - 1), h->B);
-        HIP_TRY(hipGetLastError());
+        QLE_TRY(launch(h, k_fill_i32<int32_t>, grid_for(h, 256), dim3(256), 0, h->hist_first, (int32_t)(h->tick - 1), h->B));
         HIP_TRY(hipMemcpyAsync(h->mr_anchor, state_cur(h), slot_bytes(h), hipMemcpyDeviceToDevice, h->stream));
         h->e_tick = h->e_want = h->last_mr_launch = -1;
     }
@@ -588,10 +637,7 @@ static int advance_tick(qle_batch* h)
         if (shift <= 0) return QLE_OK;
         int32_t* arrs[2] = {h->last_corr, h->hist_first};
         for (int32_t* a : arrs)
-            if (a) {
-                hipLaunchKernelGGL(k_rebase_ticks<int32_t>, grid_for(h, 256), dim3(256), 0, h->stream, a, (int32_t)shift, h->B);
-                HIP_TRY(hipGetLastError());
-            }
+            if (a) QLE_TRY(launch(h, k_rebase_ticks<int32_t>, grid_for(h, 256), dim3(256), 0, a, (int32_t)shift, h->B));
         h->tick -= shift;
         h->flags_tick -= shift;
         for (int64_t* tk : {&h->e_tick, &h->e_want, &h->last_mr_launch})
@@ -754,8 +800,7 @@ extern "C" int qle_enable_gating(qle_batch* h, int32_t on)
         }
         h->last_corr = lc; h->flags = fl;
         // upds_since_correction = 0 before the next tick (EKF.cpp:77): as if tick-1 had corrected
-        hipLaunchKernelGGL(k_fill_i32<int32_t>, grid_for(h, 256), dim3(256), 0, h->stream, h->last_corr, (int32_t)(h->tick - 1), h->B);
-        HIP_TRY(hipGetLastError());
+        QLE_TRY(launch(h, k_fill_i32<int32_t>, grid_for(h, 256), dim3(256), 0, h->last_corr, (int32_t)(h->tick - 1), h->B));
     }
     h->gating = on != 0;
     return QLE_OK;
@@ -807,9 +852,7 @@ extern "C" int qle_set_uniform_measurement_age(qle_batch* h, double seconds)
 template <typename T>
 static int upds_since_t(qle_batch* h, int32_t* d_out)
 {
-    hipLaunchKernelGGL((k_upds_since<T>), grid_for(h, 256), dim3(256), 0, h->stream, (const T*)state_cur(h), (const int32_t*)h->last_corr, (int32_t)h->tick, d_out, h->B);
-    HIP_TRY(hipGetLastError());
-    return QLE_OK;
+    return launch(h, k_upds_since<T>, grid_for(h, 256), dim3(256), 0, (const T*)state_cur(h), (const int32_t*)h->last_corr, (int32_t)h->tick, d_out, h->B);
 }
 // NODE.cpp:192-281 in one call: the gathers above composed into one struct per filter (host side; the device work is theirs).
 extern "C" int qle_get_node_report(qle_batch* h, qle_node_report* out)
@@ -884,11 +927,9 @@ static int seed_t(qle_batch* h, int reinit)
 {
     const qle_derived& d = h->der;
     QLE_TRY(mr_prepare(h));   // a pending whole-batch history restart first; the seeded filters then restart theirs
-    hipLaunchKernelGGL((k_seed<T>), grid_for(h, 256), dim3(256), 0, h->stream, dev<T>(h), (const T*)h->tick_z, (T*)state_cur(h),
-                       (T)d.cov_init[0], (T)d.cov_init[3], (T)d.cov_init[6], (T)d.cov_init[9], (T)d.cov_init[12], reinit, (int32_t)h->tick,
-                       h->last_corr, h->mr ? h->hist_first : (int32_t*)nullptr, h->mr ? (T*)h->mr_anchor : (T*)nullptr, h->B);
-    HIP_TRY(hipGetLastError());
-    return QLE_OK;
+    return launch(h, k_seed<T>, grid_for(h, 256), dim3(256), 0, dev<T>(h), (const T*)h->tick_z, (T*)state_cur(h), (T)d.cov_init[0], (T)d.cov_init[3],
+                  (T)d.cov_init[6], (T)d.cov_init[9], (T)d.cov_init[12], reinit, (int32_t)h->tick, h->last_corr, h->mr ? h->hist_first : (int32_t*)nullptr,
+                  h->mr ? (T*)h->mr_anchor : (T*)nullptr, h->B);
 }
 extern "C" int qle_initialize_state_masked(qle_batch* h, const double* z, const uint8_t* mask, int32_t reinit_bias)
 {
@@ -929,9 +970,8 @@ static int report_t(qle_batch* h, double* pose, double* cov, double* vel, double
         double* s_cov = s_pose + n * 7;
         double* s_vel = s_cov + n * 36;
         double* s_bias = s_vel + n * 3;
-        hipLaunchKernelGGL((k_report_off<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, dev<T>(h), (const T*)state_cur(h),
-                           h->pfp_on ? (const T*)h->pfp : (const T*)nullptr, s_pose, s_cov, s_vel, s_bias, i0, n);
-        HIP_TRY(hipGetLastError());
+        QLE_TRY(launch(h, k_report_off<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, dev<T>(h), (const T*)state_cur(h),
+                       h->pfp_on ? (const T*)h->pfp : (const T*)nullptr, s_pose, s_cov, s_vel, s_bias, i0, n));
         if (pose) HIP_TRY(hipMemcpyAsync(pose + i0 * 7, s_pose, (size_t)n * 7 * 8, hipMemcpyDeviceToHost, h->stream));
         if (cov) HIP_TRY(hipMemcpyAsync(cov + i0 * 36, s_cov, (size_t)n * 36 * 8, hipMemcpyDeviceToHost, h->stream));
         if (vel) HIP_TRY(hipMemcpyAsync(vel + i0 * 3, s_vel, (size_t)n * 3 * 8, hipMemcpyDeviceToHost, h->stream));
@@ -949,9 +989,7 @@ extern "C" int qle_get_report(qle_batch* h, double* pose, double* pose_cov, doub
 template <typename T>
 static int nonfinite_t(qle_batch* h)
 {
-    hipLaunchKernelGGL((k_count_nonfinite<T>), grid_for(h, 256), dim3(256), 0, h->stream, (const T*)state_cur(h), h->counter, h->B, h->compact ? kXW + kPWc : kXW + kPW);
-    HIP_TRY(hipGetLastError());
-    return QLE_OK;
+    return launch(h, k_count_nonfinite<T>, grid_for(h, 256), dim3(256), 0, (const T*)state_cur(h), h->counter, h->B, h->compact ? kXW + kPWc : kXW + kPW);
 }
 extern "C" int qle_count_nonfinite(qle_batch* h, int64_t* count)
 {
@@ -1046,9 +1084,7 @@ static int unpack_z(qle_batch* h, const void* src, double* z, uint8_t* mask)
 {
     for (int64_t i0 = 0; i0 < h->B; i0 += kStageFilters) {
         const int64_t n = std::min(kStageFilters, h->B - i0);
-        hipLaunchKernelGGL((k_unpack_z_off<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const T*)src, h->stage, h->stage_mask,
-                           i0, n);
-        HIP_TRY(hipGetLastError());
+        QLE_TRY(launch(h, k_unpack_z_off<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const T*)src, h->stage, h->stage_mask, i0, n));
         if (z) HIP_TRY(hipMemcpyAsync(z + i0 * 7, h->stage, (size_t)n * 7 * 8, hipMemcpyDeviceToHost, h->stream));
         if (mask) HIP_TRY(hipMemcpyAsync(mask + i0, h->stage_mask, (size_t)n, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1143,12 +1179,10 @@ static int synth_t(qle_batch* h, qle_inputs* in, const qle_synth_cfg* c)
     {
         if (c->perturb_filter_params && !h->pfp) e = hipMalloc(&h->pfp, kFW * (size_t)h->Bp * h->wsz);
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((k_synth<T>), grid_for(h, 64), dim3(64), 0, h->stream, a, (const int32_t*)d_slot, (T*)in->u, (T*)in->z, (T*)h->tick_z,
-                           c->perturb_filter_params ? (T*)h->pfp : (T*)nullptr, (double*)in->truth, (double*)in->truth_bias);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(QLE_ERR_HIP, "synthetic generator: %s", hipGetErrorString(e));
+    QLE_TRY(launch(h, k_synth<T>, grid_for(h, 64), dim3(64), 0, a, (const int32_t*)d_slot, (T*)in->u, (T*)in->z, (T*)h->tick_z,
+                   c->perturb_filter_params ? (T*)h->pfp : (T*)nullptr, (double*)in->truth, (double*)in->truth_bias));
+    e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail(QLE_ERR_HIP, "synthetic generator: %s", hipGetErrorString(e));
     if (c->perturb_filter_params) h->pfp_on = true;
     in->has_truth = true;
@@ -1181,9 +1215,7 @@ extern "C" int qle_synth_get_truth(qle_batch* h, const qle_inputs* in, double* p
 template <typename T>
 static int rmse_t(qle_batch* h, const qle_inputs* in, double* d_out)
 {
-    hipLaunchKernelGGL((k_rmse<T>), grid_for(h, 256), dim3(256), 0, h->stream, (const T*)state_cur(h), (const double*)in->truth, d_out, h->B);
-    HIP_TRY(hipGetLastError());
-    return QLE_OK;
+    return launch(h, k_rmse<T>, grid_for(h, 256), dim3(256), 0, (const T*)state_cur(h), (const double*)in->truth, d_out, h->B);
 }
 extern "C" int qle_synth_rmse(qle_batch* h, const qle_inputs* in, double out[3])
 {

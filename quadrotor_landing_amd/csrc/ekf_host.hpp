@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -286,10 +287,15 @@ template <int... Vs, typename F> static inline int with_int(int v, F&& f)
 // makes (a 256-thread split workgroup; a smaller value could lower another handle's limit), and each handle lists the kernels it raised
 // it for.  A handle has one device (made current by check_handle) and one host thread: the list needs no lock, and a launch of a listed
 // kernel makes no extra runtime call.
+// Every kernel launch of the library goes through here, so the launch census (qle_launch_census_begin / _end, ekf_capi.hip) sees each
+// one: while it is off it costs one relaxed atomic load.
 constexpr size_t kMaxSplitLds = (size_t)(kBlock / kTile) * kMrLdsPerWave;
+extern std::atomic<bool> g_census_on;
+void census_record(const void* kernel);
 template <typename K, typename... Args>
 static inline int launch(qle_batch* h, K* kernel, dim3 grid, dim3 block, size_t lds, const Args&... args)
 {
+    if (g_census_on.load(std::memory_order_relaxed)) census_record(reinterpret_cast<const void*>(kernel));
     if (lds > 65536) {
         const void* k = reinterpret_cast<const void*>(kernel);
         constexpr int n = (int)(sizeof(h->lds_raised) / sizeof(h->lds_raised[0]));
