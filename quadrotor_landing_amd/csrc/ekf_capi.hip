@@ -4,6 +4,7 @@
 // reference), AoS<->quad-row staging, launches on the handle's own stream.
 // There is deliberately no CPU compute path in this file.
 #include "ekf_host.hpp"
+#include "ekf_helper_kernels.hpp"
 #include "ekf_innov.hpp"
 #include "synth_kernels.hpp"
 
@@ -190,7 +191,7 @@ extern "C" int qle_set_params(qle_batch* h, const qle_params* p)
     qle_derived d;
     QLE_TRY(qle_params_derive(p, &d));
     // The state is one record array, updated in place.  The multirate EKF (EKF.cpp:196-236) keeps its history next to it: an IMU
-    // ring, a state checkpoint every mr_k ticks and one anchor slot (k_step_mr, ekf_kernels.hpp), sized for the largest step delay
+    // ring, a state checkpoint every mr_k ticks and one anchor slot (k_step_mr, ekf_multirate.hpp), sized for the largest step delay
     // the parameters allow (EKF.cpp:199-201).  Everything is allocated into locals; the handle changes only when all of it exists.
     const bool mr = p->multirate_ekf != 0;
     int32_t Nc = 0, Cu = 0;
@@ -237,7 +238,7 @@ extern "C" int qle_set_params(qle_batch* h, const qle_params* p)
         h->hist_first = hf; h->stamp = stp; h->delay_cur = dc; h->mr_u = mu; h->mr_ckpt = mc; h->mr_anchor = ma;
         h->mr_Nc = Nc; h->mr_Cu = Cu;
     }
-    // Record layout (ekf_kernels.hpp): est_bias = false without the multirate history keeps only the 9 x 9 pose block of P (compact
+    // Record layout (ekf_layout.hpp): est_bias = false without the multirate history keeps only the 9 x 9 pose block of P (compact
     // records, 64 words moved per direction instead of 136) on the batch sizes the lane-per-filter kernels serve; the workgroup-cooperative
     // kernels of the small batches (latency-bound, not byte-bound) and the multirate history work on full records.  QLE_COMPACT=0|1 forces it.
     // fp32 small batches: the cooperative kernel only where ticks with tag poses are frequent (see qle_create)

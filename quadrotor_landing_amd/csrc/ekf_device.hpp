@@ -134,6 +134,10 @@ __host__ __device__ constexpr int level_first_word(int b, int vw)
     }
     return w0;
 }
+// The triangle split between two homes (ekf_split.hpp): block-rows r and v in one, th, ab and wb in the other.  Here because the host
+// sizes the dynamic LDS of the kernels that use it from these alone (ekf_layout.hpp).
+constexpr int kTopWords = 75;   // rows r (42) and v (33)
+constexpr int kLoWords = 45;    // rows th (24), ab (15), wb (6)
 #define QLE_PS(i, j) P[::qle::sidx((i), (j))]
 
 // Uniform (per-launch) parameters in the compute dtype; derived on the host by
@@ -152,7 +156,7 @@ struct DevParams {
     T R[6];          // diag(R_r,R_ang) (EKF.cpp:116-118)
     T ab_static[3];  // EKF.cpp:357
     T wb_static[3];  // EKF.cpp:358
-    int32_t compact; // state records hold the 9 x 9 pose block of P only (est_bias = false, EKF.cpp:92; ekf_kernels.hpp)
+    int32_t compact; // state records hold the 9 x 9 pose block of P only (est_bias = false, EKF.cpp:92; ekf_layout.hpp)
 };
 
 // Noise / static-bias values a tick actually uses: shared or per filter (cfg 5).

@@ -20,7 +20,8 @@
 #include <type_traits>
 #include <vector>
 
-#include "ekf_kernels.hpp"
+#include "ekf_gate.hpp"
+#include "ekf_layout.hpp"
 
 using namespace qle;
 
@@ -53,7 +54,7 @@ struct qle_batch {
     int32_t dtype = QLE_F32;
     int32_t device = 0;
     int32_t block = 256;
-    int32_t split = 0;        // nt == 3: which workgroups keep their tiles cached (cached_workgroup() in ekf_kernels.hpp)
+    int32_t split = 0;        // nt == 3: which workgroups keep their tiles cached (cached_workgroup() in ekf_layout.hpp)
     int32_t nt_refresh = 0;   // > 0: nt == 1 and the state is <= 40 MiB: non-temporal stores, cached-store tick every nt_refresh ticks
     int32_t nt = 0;        // cache policy of the hot kernels' state accesses: 0 cached, 1 L2-sized scheme (effective_nt), 2 non-temporal, 3 split
     bool quad_auto = true; // quad follows the rules of qle_create / qle_set_params (false: QLE_QUAD given)
@@ -80,7 +81,7 @@ struct qle_batch {
     uint8_t* stage_mask = nullptr;
     unsigned long long* counter = nullptr;
     bool state_set = false;
-    bool compact = false;       // records hold the 9 x 9 pose block of P only (est_bias = false; qle_set_params, ekf_kernels.hpp)
+    bool compact = false;       // records hold the 9 x 9 pose block of P only (est_bias = false; qle_set_params, ekf_layout.hpp)
     // device-side measurement gating (EKF.cpp:147-186)
     bool gating = false;
     int32_t* last_corr = nullptr;  // [B] index of each filter's last correcting tick, -1 = never
@@ -97,7 +98,7 @@ struct qle_batch {
     void* mr_ckpt = nullptr;       // state checkpoints: mr_Nc slots, one per mr_k ticks
     void* mr_anchor = nullptr;     // one state slot: every filter's corrected entry at hist_first
     int32_t mr_k = 32, mr_Nc = 0, mr_Cu = 0;
-    // the extra checkpoint (slot mr_Nc), placed at the expected entry of the next measurement (k_step_mr, ekf_kernels.hpp)
+    // the extra checkpoint (slot mr_Nc), placed at the expected entry of the next measurement (k_step_mr, ekf_multirate.hpp)
     int64_t e_tick = -1;           // tick whose state the slot holds, -1 = none
     int64_t e_want = -1;           // the predict launch of this tick fills it, -1 = none scheduled
     int64_t last_mr_launch = -1;   // tick of the last launch of k_step_mr (the cadence of the tag poses as the host sees it)
@@ -309,7 +310,8 @@ static inline int launch(qle_batch* h, K* kernel, dim3 grid, dim3 block, size_t 
     return QLE_OK;
 }
 
-// ---- kernel launchers, explicitly instantiated for float and double in the tu_*.hip files ----
+// ---- kernel launchers, explicitly instantiated for float and double in the tu_*.hip files (the bodies of the lane-per-filter ones:
+// ekf_lane_launch.hpp) ----
 int mr_prepare(qle_batch* h);                                                                  // ekf_capi
 template <typename T> int launch_step_mr(qle_batch* h, const void* u, const void* z);          // tu_misc: k_step_mr
 template <typename T> int launch_innov(qle_batch* h, void* z, bool gate, double chi2_max);     // tu_predict: k_innov
@@ -336,78 +338,3 @@ template <typename T> static inline int run_resident_t(qle_batch* h, const qle_i
 {
     return h->compact ? resident_lanes<T, true>(h, in, t0, n) : resident_lanes<T, false>(h, in, t0, n);
 }
-
-#ifdef QLE_TU_T
-// The bodies of the lane-per-filter launchers, seen by the tu_*.hip units only: each unit instantiates its side, and ekf_capi.hip
-// (which sees the declarations above) instantiates no kernel.
-
-// prediction_step from `src` into `dst`; history: the tick also appends to the multirate history (full records only: compact records
-// never carry it, qle_set_params).
-template <typename T, bool COMPACT>
-int predict_lanes(qle_batch* h, const void* u, const void* src, void* dst, bool history)
-{
-    const DevParams<T>& p = dev<T>(h);
-    const dim3 g = grid_for(h, h->block), b(h->block);
-    T* acc = h->aux ? (T*)h->aux_accel : (T*)nullptr;
-    history = history && !COMPACT;
-    // multirate history of this tick: the IMU sample's ring slot and, on checkpoint ticks, the checkpoint slot
-    T* hu = history ? (T*)mr_u_slot_host(h, h->tick) : (T*)nullptr;
-    bool extra_ck = false;
-    T* hc = history ? (T*)mr_ck_for_predict(h, h->tick, &extra_ck) : (T*)nullptr;
-    // the extra checkpoint stays in the Infinity Cache when it fits there next to the state (cached stores), else it is streamed
-    const int32_t ck_cached = extra_ck && 2 * slot_bytes(h) <= ((size_t)200 << 20) ? 1 : 0;
-    // "loads first" (predict_tick): the fp32 tick of a batch that gives every SIMD at most one wave
-    return with_bool(h->pfp_on, [&](auto F) {
-    return with_int<0, 1, 2, 3>(effective_nt(h), [&](auto N) {
-    return with_bool_if<!COMPACT>(history, [&](auto M) {
-    return with_bool_if<sizeof(T) == 4 && !COMPACT>(h->loads_first, [&](auto L) {
-        return launch(h, k_predict<T, F, N, M, COMPACT, L>, g, b, 0, (const T*)src, (T*)dst, (const T*)u, h->B, (int64_t)0, (int32_t)g.x,
-                      (int32_t)b.x, h->split, ck_cached, (const T*)h->pfp, acc, hu, hc, p);
-    }); }); }); });
-}
-
-template <typename T, bool COMPACT>
-int step_lanes(qle_batch* h, const void* u, const void* z)
-{
-    const DevParams<T>& p = dev<T>(h);
-    const GateParams gp = make_gate(h);
-    const dim3 g = grid_for(h, h->block), b(h->block);
-    T *st = (T*)state_cur(h), *acc = h->aux ? (T*)h->aux_accel : (T*)nullptr, *obs = h->aux ? (T*)h->aux_obs : (T*)nullptr;
-    return with_bool(h->pub.direct_orien_method, [&](auto D) {
-    return with_bool(h->gating, [&](auto G) {
-    return with_bool(h->pfp_on, [&](auto F) {
-    return with_int<0, 1, 2, 3>(effective_nt(h), [&](auto N) {
-        return launch(h, k_step<T, D, F, G, N, COMPACT>, g, b, 0, st, (const T*)u, (const T*)z, h->B, (int64_t)0, (int32_t)g.x, (int32_t)b.x,
-                      h->split, (const T*)h->pfp, acc, obs, h->last_corr, h->flags, p, gp);
-    }); }); }); });
-}
-
-template <typename T, bool COMPACT>
-int update_lanes(qle_batch* h, const void* z)
-{
-    const DevParams<T>& p = dev<T>(h);
-    const dim3 g = grid_for(h, h->block), b(h->block);
-    T *st = (T*)state_cur(h), *obs = h->aux ? (T*)h->aux_obs : (T*)nullptr;
-    return with_bool(h->pub.direct_orien_method, [&](auto D) {
-    return with_bool(h->pfp_on, [&](auto F) {
-        return launch(h, k_update<T, D, F, COMPACT>, g, b, split_lds<T>(h), st, (const T*)z, h->B, (int32_t)g.x, (int32_t)b.x, (const T*)h->pfp,
-                      obs, p);
-    }); });
-}
-
-// On-chip-resident variant: ONE launch advances every filter by n ticks with x and P held in
-// registers; HBM traffic is the state once plus the inputs.  Not the unit of work of the headline
-// metric (one launch per tick); reported separately.
-template <typename T, bool COMPACT>
-int resident_lanes(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n)
-{
-    const DevParams<T>& p = dev<T>(h);
-    const dim3 g = grid_for(h, h->block), b(h->block);
-    const int64_t pu = (int64_t)(in->pitch_u / h->wsz), pz = (int64_t)(in->pitch_z / h->wsz);
-    return with_bool(h->pub.direct_orien_method, [&](auto D) {
-    return with_bool(h->pfp_on, [&](auto F) {
-        return launch(h, k_run_resident<T, D, F, COMPACT>, g, b, split_lds<T>(h), p, (T*)state_cur(h), (const T*)in->u, (const T*)in->z,
-                      (const int32_t*)in->d_slot, pu, pz, in->T, t0, n, (const T*)h->pfp, h->B);
-    }); });
-}
-#endif

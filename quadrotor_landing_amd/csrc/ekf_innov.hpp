@@ -19,7 +19,7 @@
 
 #include <utility>
 
-#include "ekf_kernels.hpp"
+#include "ekf_layout.hpp"
 
 namespace qle {
 
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void k_innov(const T* __restrict__ st, T* _
                                                   const T* __restrict__ pfp, T* __restrict__ diag, T* __restrict__ nis_out, double chi2_max,
                                                   DevParams<T> p)
 {
-    QLE_ARGS_EARLY(st, zs, B, grid_x, block_x);
+    args_early(st, zs, B, grid_x, block_x);
     const int64_t i = batch_block((unsigned)grid_x) * block_x + threadIdx.x;
     if (i >= B) return;
     T zr[kZW];

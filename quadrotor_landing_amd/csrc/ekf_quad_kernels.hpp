@@ -1,6 +1,6 @@
 // ekf_quad_kernels.hpp -- the workgroup-cooperative tick kernel (arithmetic: ekf_quad.hpp), gfx950.
 //
-// Same HBM layout as the one-lane-per-filter kernels (wave tiles of 64 filters, ekf_kernels.hpp) and the same
+// Same HBM layout as the one-lane-per-filter kernels (wave tiles of 64 filters, ekf_layout.hpp) and the same
 // per-tick traffic.  A 256-thread workgroup is ONE tile and every thread has up to two roles:
 //
 //   quad role   (all four waves)  thread t is lane t%4 of the quad of filter t/4: lanes 0..2 load / store the ten
@@ -20,8 +20,10 @@
 // fp64 needs no scratch (45 covariance values per lane instead of 120).
 #pragma once
 
-#include "ekf_kernels.hpp"
+#include "ekf_gate.hpp"
+#include "ekf_layout.hpp"
 #include "ekf_quad.hpp"
+#include "ekf_stamps.hpp"
 
 namespace qle {
 
@@ -101,16 +103,10 @@ __device__ __forceinline__ void quad_store_P(T* __restrict__ tb, int f, int j, c
         }
     }
 }
-// Register budget: at least WgWaves waves per SIMD (512 / WgWaves registers per lane).
+// Register budget: at least kWgWaves waves per SIMD (512 / kWgWaves registers per lane): two for fp32, one for fp64.
 // Measured (profiles/r02_tuning.md): fp32 fits 128 registers (four waves per SIMD) only for the predict-only instantiation;
 // fp64 needs the whole file (256 VGPRs + AGPRs, one wave per SIMD) to stay out of scratch memory.
-#ifndef QLE_WG_WAVES_F32
-#define QLE_WG_WAVES_F32 2
-#endif
-#ifndef QLE_WG_WAVES_F64
-#define QLE_WG_WAVES_F64 1
-#endif
-template <typename T> struct WgWaves { static constexpr int value = sizeof(T) == 4 ? QLE_WG_WAVES_F32 : QLE_WG_WAVES_F64; };
+template <typename T> constexpr int kWgWaves = sizeof(T) == 4 ? 2 : 1;
 
 // One tick of tile `tile` by its workgroup: predict, and with STEP correct where the tag record's mask word is set (GATE:
 // where filter_update's decision logic says so, EKF.cpp:147-186).  In place on `st`.  A filter whose stored quaternion is
@@ -404,17 +400,17 @@ __device__ __forceinline__ void wg_tick(const DevParams<T>& p, const GateParams&
 // Grid: one 256-thread workgroup per FPW filters (a tile, or a quarter of one).  NT as in k_predict / k_step (3 = cached / streamed split
 // per workgroup).
 template <typename T, bool DIRECT, bool PFP, bool GATE, bool STEP, int NT, int FPW>
-__global__ __launch_bounds__(kBlock, WgWaves<T>::value) void kw_tick(T* st, const T* __restrict__ us, const T* __restrict__ zs, int64_t B, int32_t grid_x, int32_t split,   // (argument order: see k_predict)
+__global__ __launch_bounds__(kBlock, kWgWaves<T>) void kw_tick(T* st, const T* __restrict__ us, const T* __restrict__ zs, int64_t B, int32_t grid_x, int32_t split,   // (argument order: see k_predict)
                                                                       const T* __restrict__ pfp, T* __restrict__ aux_accel, T* __restrict__ aux_obs,
                                                                       int32_t* __restrict__ last_corr, uint8_t* __restrict__ flags, DevParams<T> p, GateParams gp)
 {
     __shared__ T lds[FPW * kLdsStride + 2];   // the per-filter records + the workgroup's "somebody corrects" word
-    QLE_ARGS_EARLY(st, us, zs, B, grid_x);
+    args_early(st, us, zs, B, grid_x);
     constexpr int PER = kTile / FPW;
     const int64_t wg = batch_block((unsigned)grid_x);
     const int64_t tile = wg / PER;
     const int f0 = (int)(wg % PER) * FPW;
-    if (NT == 3) {
+    if (NT == 3) {   // (not through with_policy(): the lambda around wg_tick changes the generated code of every instantiation)
         if (cached_workgroup(split)) wg_tick<T, DIRECT, PFP, GATE, STEP, 0, FPW>(p, gp, st, us, zs, pfp, aux_accel, aux_obs, last_corr, flags, B, tile, f0, lds);
         else wg_tick<T, DIRECT, PFP, GATE, STEP, 2, FPW>(p, gp, st, us, zs, pfp, aux_accel, aux_obs, last_corr, flags, B, tile, f0, lds);
     } else {

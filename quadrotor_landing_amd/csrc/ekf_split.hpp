@@ -28,12 +28,10 @@
 #include "ekf_packed.hpp"
 
 // Between two phases of the split algebra: nothing is scheduled across (the backend would otherwise hoist the next phase's LDS reads over
-// the current one and hold both block sets in registers).
-#ifndef QLE_FENCE_MASK
-#define QLE_FENCE_MASK 0   // sched_barrier mask: which instruction classes MAY still cross (0: none; 2 | 4: VALU and SALU)
-#endif
+// the current one and hold both block sets in registers).  The correction has one between its halves, between the block-rows of each
+// downdate and between every 3 x 3 block of the LDS rows.
 #if defined(__HIP_DEVICE_COMPILE__)
-#define QLE_PHASE_FENCE() __builtin_amdgcn_sched_barrier(QLE_FENCE_MASK)
+#define QLE_PHASE_FENCE() __builtin_amdgcn_sched_barrier(0)
 #else
 #define QLE_PHASE_FENCE() do { } while (0)
 #endif
@@ -55,36 +53,9 @@ namespace qle { static __device__ unsigned long long qle_dbg_split_clock[4096 * 
 #define QLE_SPLIT_STAMP(k, dep) do { } while (0)
 #endif
 
-// The fences inside the predict (the per-tick part of the replay loop) have their own switch.  They are OFF: with MachineLICM off for the
-// unit (Makefile) the predict needs none to stay out of scratch, and without them the backend overlaps the nominal-state chain with
-// the LDS round trips of block-row r (k_step_mr<double> 94.0 -> 89.6 us, profiles/r04_tuning.md section 2).  The correction keeps its fences.
-#ifndef QLE_PREDICT_FENCES
-#define QLE_PREDICT_FENCES 0
-#endif
-// fences of the correction: 2 = between every 3 x 3 block of the LDS rows, 1 = between block-rows and halves only, 0 = none
-#ifndef QLE_UPDATE_FENCES
-#define QLE_UPDATE_FENCES 2
-#endif
-#if QLE_UPDATE_FENCES >= 2
-#define QLE_BLOCK_FENCE() QLE_PHASE_FENCE()
-#else
-#define QLE_BLOCK_FENCE() do { } while (0)
-#endif
-#if QLE_UPDATE_FENCES >= 1
-#define QLE_UPDATE_FENCE() QLE_PHASE_FENCE()
-#else
-#define QLE_UPDATE_FENCE() do { } while (0)
-#endif
-#if QLE_PREDICT_FENCES
-#define QLE_PREDICT_FENCE() QLE_PHASE_FENCE()
-#else
-#define QLE_PREDICT_FENCE() do { } while (0)
-#endif
-
 namespace qle {
 
-constexpr int kTopWords = 75;   // rows r (42) and v (33)
-constexpr int kLoWords = 45;    // rows th (24), ab (15), wb (6)
+// (kTopWords / kLoWords, the sizes of the two homes: ekf_device.hpp)
 
 // Upper triangle of a symmetric 3x3: (0,0) (0,1) (0,2) (1,1) (1,2) (2,2).
 __host__ __device__ constexpr int sym3(int i, int j) { return i <= j ? i * 3 - i * (i - 1) / 2 + (j - i) : j * 3 - j * (j - 1) / 2 + (i - j); }
@@ -173,6 +144,9 @@ __host__ __device__ __forceinline__ void split_nominal(const DevParams<T>& p, co
 }
 
 // P <- F P F^T + W Q W^T (EKF.cpp:412-414), top-down in place.
+// No phase fence between the block-rows here (the per-tick part of the replay loop): with MachineLICM off for the unit (Makefile) the
+// predict needs none to stay out of scratch, and without them the backend overlaps the nominal-state chain with the LDS round trips of
+// block-row r (k_step_mr<double> 94.0 -> 89.6 us, profiles/r04_tuning.md section 2).  The correction keeps its fences.
 template <typename T, class Top>
 __host__ __device__ __forceinline__ void split_predict_cov(const SplitCtx<T>& s, const Noise<T>& nz, Top& top, T (&lo)[kLoWords])
 {
@@ -229,7 +203,6 @@ __host__ __device__ __forceinline__ void split_predict_cov(const SplitCtx<T>& s,
         for (int k = 0; k < 9; ++k) top.st(T_RW + k, Mw[k]);
     }
     QLE_SPLIT_STAMP(1, lo[0]);
-    QLE_PREDICT_FENCE();
     // ---- block-row v ------------------------------------------------------------------------------------------------------------
     {
         T Mw[9], Ma[9], Mt[9], vto[9], vao[9];
@@ -290,7 +263,6 @@ __host__ __device__ __forceinline__ void split_predict_cov(const SplitCtx<T>& s,
         for (int k = 0; k < 9; ++k) top.st(T_VW + k, Mw[k]);
     }
     QLE_SPLIT_STAMP(2, lo[0]);
-    QLE_PREDICT_FENCE();
     // ---- block-row th (registers) -----------------------------------------------------------------------------------------------
     {
         T N[9], tw[9], ta[9];
@@ -413,7 +385,7 @@ __host__ __device__ __forceinline__ void ekf_update_split(const DevParams<T>& p,
     }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-        QLE_UPDATE_FENCE();
+        QLE_PHASE_FENCE();
         if (half == 1) {   // the th columns of P1, less V1 Cx, take V1's place row by row
 #pragma unroll
             for (int a = 0; a < 15; ++a) {
@@ -440,7 +412,7 @@ __host__ __device__ __forceinline__ void ekf_update_split(const DevParams<T>& p,
         // P(i, k) += sum_m (-V(i, m) / d_m) V(k, m), block-row by block-row; the LDS rows pass through registers one block at a time
 #pragma unroll
         for (int b = 0; b < 5; ++b) {
-            QLE_UPDATE_FENCE();
+            QLE_PHASE_FENCE();
             T NV[3][3];
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
@@ -449,7 +421,7 @@ __host__ __device__ __forceinline__ void ekf_update_split(const DevParams<T>& p,
             }
 #pragma unroll
             for (int c = b; c < 5; ++c) {
-                if (b < 2 && c > b) QLE_BLOCK_FENCE();
+                if (b < 2 && c > b) QLE_PHASE_FENCE();
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -465,7 +437,7 @@ __host__ __device__ __forceinline__ void ekf_update_split(const DevParams<T>& p,
             }
         }
     }
-    QLE_UPDATE_FENCE();
+    QLE_PHASE_FENCE();
     quad::update_inject<SQ, T>(p, x, dx);   // EKF.cpp:486-501
 }
 

@@ -11,7 +11,7 @@
 // to the compute dtype on store.  Not on the timed hot path.
 #pragma once
 
-#include "ekf_kernels.hpp"
+#include "ekf_layout.hpp"
 
 namespace qle {
 

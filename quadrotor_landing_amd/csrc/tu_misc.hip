@@ -1,6 +1,7 @@
-// tu_misc.hip -- launchers of k_step_mr, k_update, k_run_resident (the bodies of the last two are in ekf_host.hpp)
+// tu_misc.hip -- launchers of k_step_mr, k_update, k_run_resident (the bodies of the last two are in ekf_lane_launch.hpp)
 // Compiled once per compute dtype (-DQLE_TU_T=float|double); see ekf_host.hpp.
-#include "ekf_host.hpp"
+#include "ekf_lane_launch.hpp"
+#include "ekf_multirate.hpp"
 #ifndef QLE_TU_T
 #error "compile with -DQLE_TU_T=float or -DQLE_TU_T=double"
 #endif

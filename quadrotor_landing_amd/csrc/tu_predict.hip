@@ -1,7 +1,7 @@
-// tu_predict.hip -- launchers of k_predict (one lane per filter, predict-only tick; the body is in ekf_host.hpp) and of k_innov
+// tu_predict.hip -- launchers of k_predict (one lane per filter, predict-only tick; the body is in ekf_lane_launch.hpp) and of k_innov
 // (innovation diagnostics and the chi-square gate, ekf_innov.hpp).  Compiled once per compute dtype (-DQLE_TU_T=float|double); see
 // ekf_host.hpp.
-#include "ekf_host.hpp"
+#include "ekf_lane_launch.hpp"
 #include "ekf_innov.hpp"
 
 #ifndef QLE_TU_T

@@ -1,7 +1,7 @@
 """est_bias = false (relative_pose_EKF.cpp:92, num_states = 9; :405-409): COMPACT state records.
 
 A filter that does not estimate the biases has identically zero bias blocks in P; on the batch sizes the lane-per-filter kernels
-serve, its record then keeps only the 45 words of the 9 x 9 pose block (ekf_kernels.hpp, `load_P_compact`) and a tick moves
+serve, its record then keeps only the 45 words of the 9 x 9 pose block (ekf_layout.hpp, `load_P_compact`) and a tick moves
 16 + 48 words per direction instead of 136.  The arithmetic is the same register image either way, so a compact handle must agree
 with a full-record handle BIT FOR BIT on the tick kernels (the separately compiled on-chip-resident kernel: to rounding in fp32), and with
 the reference twin's `nobias` goldens within the usual tolerances.

@@ -1027,7 +1027,7 @@ def test_static_bias_predict_against_twin_identity(dtype, tol):
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 @pytest.mark.parametrize("mr", [0, 1])
 def test_multi_tag_gate_against_composed_twin_decisions(dtype, mr):
-    """EKF.cpp:160-181 on the device (corner_gate, ekf_kernels.hpp): the 13-tag bundle of HW.yaml == `or` over the twin's
+    """EKF.cpp:160-181 on the device (corner_gate, ekf_gate.hpp): the 13-tag bundle of HW.yaml == `or` over the twin's
     single-tag decisions, and each tag alone == the twin's decision for it, on 320 tag poses."""
     d = np.load(f"{GOLDEN}/branch_cases.npz")
     Z, per_tag, composed = d["gate__z"], d["gate__per_tag"], d["gate__composed"]
