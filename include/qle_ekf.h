@@ -332,6 +332,44 @@ int qle_get_policy(const qle_batch *h, qle_policy *out);
  * kind 0 = predict tick, 1 = fused predict+update tick, 2 = stand-alone update. */
 int64_t qle_algorithmic_bytes(const qle_batch *h, int32_t kind);
 
+/* ---- device view: where the handle's records live in GPU memory ----------------
+ * For code that feeds or reads the engine from GPU memory without passing through the host (include/qle_devio.h is
+ * built on these two calls alone).  The pointers obey the wave-tile layout DESIGN.md section 3 publishes: word w of
+ * filter i of an array of WT-word records of the compute dtype is at
+ *     off(w, i) = (i/64)*WT*64 + ((w/VW)*64 + i%64)*VW + w%VW,   VW = 4 (fp32) / 2 (fp64),
+ * a record whose length is not a multiple of VW (fp32 IMU record: 6 words) ending in one row of the remaining words
+ * per filter; every array is allocated for padded_batch filters (whole 64-filter tiles).  Work on these pointers is
+ * ordered with the handle's own work by running on `stream`, or by HIP events against it.  Both calls only read the
+ * handle: no state changes, nothing is launched, nothing synchronises.  The caller sets struct_size = sizeof(struct)
+ * before the call (a smaller value is refused). */
+typedef struct qle_device_view {
+    uint32_t struct_size;
+    int32_t device;          /* HIP device index                                         */
+    void *stream;            /* hipStream_t of the handle                                */
+    int32_t dtype;           /* compute dtype of every record: QLE_F32 | QLE_F64         */
+    int32_t num_states;      /* n of P = [n][n]: 15 or 9 (EKF.cpp:92)                    */
+    int64_t batch;
+    int64_t padded_batch;
+    void *state;             /* state records: x (16 words), packed P from word 16 on    */
+    int32_t state_words;     /* WT of the state records (144)                            */
+    int32_t record_words;    /* words of it a tick reads and writes: 136, or 64 compact  */
+    int32_t compact;         /* != 0: words 16..60 are the row-major triangle of the 9 x 9 pose block (ekf_layout.hpp) */
+    int32_t reserved;
+    const void *filter_params; /* 24-word per-filter parameter records while qle_set_filter_params is in force, else NULL */
+    double ab_static[3];     /* the static biases qle_get_report adds (NODE.cpp:215-220), as the compute dtype holds them */
+    double wb_static[3];
+} qle_device_view;
+int qle_get_device_view(qle_batch *h, qle_device_view *out);
+/* Tick t of a sequence: its IMU records (6 words per filter) and its tag records (8 words: z 7 + mask word),
+ * z = NULL when the tick has no measurement slot. */
+typedef struct qle_inputs_view {
+    uint32_t struct_size;
+    int32_t has_tag;
+    void *u;
+    void *z;
+} qle_inputs_view;
+int qle_inputs_get_device_view(const qle_inputs *in, int64_t t, qle_inputs_view *out);
+
 /* ---- launch census (diagnostics) ------------------------------------------- */
 /* Process-wide list of the distinct kernels launched since qle_launch_census_begin (all handles, all host threads).
  * qle_launch_census_end stops the census and writes the list -- the kernels' mangled names, sorted, each followed by '\n', then a

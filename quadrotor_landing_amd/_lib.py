@@ -69,6 +69,18 @@ class QlePolicy(C.Structure):
                 ("ring_slots", _i32), ("state_bytes", _i64), ("ring_bytes", _i64), ("record_words", _i32), ("reserved", _i32)]
 
 
+class QleDeviceView(C.Structure):
+    """`struct qle_device_view`: where a handle's records live in GPU memory (wave tiles)."""
+    _fields_ = [("struct_size", C.c_uint32), ("device", _i32), ("stream", C.c_void_p), ("dtype", _i32), ("num_states", _i32),
+                ("batch", _i64), ("padded_batch", _i64), ("state", C.c_void_p), ("state_words", _i32), ("record_words", _i32),
+                ("compact", _i32), ("reserved", _i32), ("filter_params", C.c_void_p), ("ab_static", _d * 3), ("wb_static", _d * 3)]
+
+
+class QleInputsView(C.Structure):
+    """`struct qle_inputs_view`: the IMU and tag records of one tick of a sequence."""
+    _fields_ = [("struct_size", C.c_uint32), ("has_tag", _i32), ("u", C.c_void_p), ("z", C.c_void_p)]
+
+
 class QleError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"qle error {code}: {msg}")
@@ -130,6 +142,8 @@ SYMBOLS = {
     "qle_timer_end": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "qle_algorithmic_bytes": (_i64, [_vp, _i32]),
     "qle_get_policy": (C.c_int, [_vp, C.POINTER(QlePolicy)]),
+    "qle_get_device_view": (C.c_int, [_vp, C.POINTER(QleDeviceView)]),
+    "qle_inputs_get_device_view": (C.c_int, [_vp, _i64, C.POINTER(QleInputsView)]),
     "qle_launch_census_begin": (C.c_int, []),
     "qle_launch_census_end": (C.c_int, [C.c_char_p, _i64, C.POINTER(_i64)]),
 }

@@ -1124,6 +1124,44 @@ extern "C" int qle_run(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n
 }
 
 
+// ---- device views (include/qle_ekf.h): where the records live, for a device-side boundary.  Host code only, read-only.
+extern "C" int qle_get_device_view(qle_batch* h, qle_device_view* out)
+{
+    if (!h || !out) return fail(QLE_ERR_INVALID, "null argument");
+    if (out->struct_size < sizeof(qle_device_view)) return fail(QLE_ERR_INVALID, "qle_device_view: struct_size %u, need %zu", out->struct_size, sizeof(qle_device_view));
+    std::memset(out, 0, sizeof(*out));
+    out->struct_size = (uint32_t)sizeof(qle_device_view);
+    out->device = h->device;
+    out->stream = (void*)h->stream;
+    out->dtype = h->dtype;
+    out->num_states = h->der.num_states;
+    out->batch = h->B;
+    out->padded_batch = h->Bp;
+    out->state = state_cur(h);
+    out->state_words = kSW;
+    out->record_words = h->compact ? kXW + kPWc : kXW + kPW;
+    out->compact = h->compact ? 1 : 0;
+    out->filter_params = h->pfp_on ? h->pfp : nullptr;
+    for (int k = 0; k < 3; ++k) {
+        out->ab_static[k] = h->dtype == QLE_F32 ? (double)h->pf.ab_static[k] : h->pd.ab_static[k];
+        out->wb_static[k] = h->dtype == QLE_F32 ? (double)h->pf.wb_static[k] : h->pd.wb_static[k];
+    }
+    return QLE_OK;
+}
+
+extern "C" int qle_inputs_get_device_view(const qle_inputs* in, int64_t t, qle_inputs_view* out)
+{
+    QLE_TRY(check_tick(in, t));
+    if (!out) return fail(QLE_ERR_INVALID, "out is null");
+    if (out->struct_size < sizeof(qle_inputs_view)) return fail(QLE_ERR_INVALID, "qle_inputs_view: struct_size %u, need %zu", out->struct_size, sizeof(qle_inputs_view));
+    const int32_t s = in->slot[(size_t)t];
+    out->struct_size = (uint32_t)sizeof(qle_inputs_view);
+    out->has_tag = s >= 0 ? 1 : 0;
+    out->u = u_at(in, t);
+    out->z = s >= 0 ? z_at(in, s) : nullptr;
+    return QLE_OK;
+}
+
 extern "C" int qle_run_resident(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n)
 {
     QLE_TRY(check_handle(h));

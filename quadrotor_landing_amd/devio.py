@@ -1,0 +1,230 @@
+"""Device-tensor boundary: tick a `BatchedRelativePoseEKF` from tensors that already live in GPU memory.
+
+`DeviceIO(ekf)` packs AoS tensors on the handle's GPU (float32 or float64) straight into the wave-tile records the tick
+kernels read, runs the existing tick (`qle_run` over a private two-tick sequence, so every mode it serves is covered:
+explicit masks, the device decision logic of `enable_gating`, multirate with a fixed or uniform-age delay), and returns
+state and report as device tensors.  No host copy and no synchronisation on the way: the work is ordered by HIP events
+between the handle's stream and the caller's current stream (include/qle_devio.h, libqle_devio.so).
+
+A tensor is a torch tensor or anything with `data_ptr()`, `dtype`, `shape`, `device` (and optionally `is_contiguous()`).
+torch is imported lazily: only to find the caller's current stream for torch tensors and to allocate outputs.
+
+Still host-fed through `BatchedRelativePoseEKF`: seeding (`initialize_state`), `set_state`, the per-filter stamps of
+`dynamic_meas_delay` (`filter_update(t_curr=..., apriltag_time=...)`) and the NIS-gated calls.
+"""
+import ctypes as C
+import os
+import sys
+
+from ._lib import QLE_F32, QleDeviceView, QleInputsView, QleError, check, lib
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+DEVIO_LIB_PATH = os.environ.get("QLE_DEVIO_LIB") or os.path.join(_HERE, "libqle_devio.so")
+
+QDV_F32, QDV_F64 = 0, 1
+_vp = C.c_void_p
+_pview, _pin = C.POINTER(QleDeviceView), C.POINTER(QleInputsView)
+# every symbol include/qle_devio.h declares: name -> (restype, argtypes)
+SYMBOLS = {
+    "qdv_last_error": (C.c_char_p, []),
+    "qdv_pack_inputs": (C.c_int, [_pview, _pin, _vp, _vp, _vp, C.c_int32]),
+    "qdv_unpack_state": (C.c_int, [_pview, _vp, _vp, C.c_int32]),
+    "qdv_unpack_report": (C.c_int, [_pview, _vp, _vp, _vp, _vp, C.c_int32]),
+    "qdv_wait_stream": (C.c_int, [_pview, _vp]),
+    "qdv_signal_stream": (C.c_int, [_pview, _vp]),
+}
+
+_dlib = None
+
+
+def devio_lib():
+    """Load libqle_devio.so; raises (never falls back) when it is missing."""
+    global _dlib
+    if _dlib is None:
+        if not os.path.exists(DEVIO_LIB_PATH):
+            raise ImportError(f"{DEVIO_LIB_PATH} not built: run `make -C quadrotor_landing_amd/csrc` (hipcc, gfx950). "
+                              "There is no fallback for the device-tensor boundary.")
+        L = C.CDLL(DEVIO_LIB_PATH)
+        for name, (res, args) in SYMBOLS.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _dlib = L
+    return _dlib
+
+
+def _dcheck(rc):
+    if rc != 0:
+        raise QleError(rc, devio_lib().qdv_last_error().decode())
+
+
+_FLOATS = {"float32": QDV_F32, "float64": QDV_F64}
+_MASKS = ("uint8", "bool")
+
+
+def _dtype_name(t):
+    return str(t.dtype).rsplit(".", 1)[-1]
+
+
+def _device_index(t):
+    """(type, index) of a tensor's device: torch.device, or a string such as 'cuda:1'."""
+    d = t.device
+    kind = getattr(d, "type", None)
+    if kind is not None:
+        idx = getattr(d, "index", None)
+    else:
+        kind, _, idx = str(d).partition(":")
+        idx = int(idx) if idx else None
+    return kind, (0 if idx is None else int(idx))
+
+
+def _is_torch(t):
+    return type(t).__module__.split(".")[0] == "torch"
+
+
+class DeviceIO:
+    def __init__(self, ekf):
+        self.ekf = ekf
+        self._float = QDV_F32 if ekf.dtype == QLE_F32 else QDV_F64
+        self._seq = None   # two ticks: 0 without a tag slot, 1 with one (made on the first tick)
+
+    # ---- argument checks (before any GPU call)
+    def _check(self, t, name, shape, dtypes):
+        for attr in ("data_ptr", "dtype", "shape", "device"):
+            if not hasattr(t, attr):
+                raise ValueError(f"{name}: expected a device tensor (data_ptr(), dtype, shape, device), got {type(t).__name__}")
+        kind, idx = _device_index(t)
+        if kind not in ("cuda", "hip") or idx != self.ekf.device:
+            raise ValueError(f"{name}: tensor is on {t.device}, the filter handle is on GPU {self.ekf.device}")
+        dn = _dtype_name(t)
+        if dn not in dtypes:
+            raise ValueError(f"{name}: dtype {t.dtype} not supported, expected one of {tuple(dtypes)}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        if hasattr(t, "is_contiguous") and not t.is_contiguous():
+            raise ValueError(f"{name}: tensor must be contiguous")
+        if t.data_ptr() % 16 != 0:
+            raise ValueError(f"{name}: tensor storage must be 16-byte aligned")
+        return dn
+
+    def _current_stream(self, *tensors):
+        """hipStream_t of the caller's current stream on the handle's device (torch's, when torch is in use), else the default stream."""
+        if any(_is_torch(t) for t in tensors if t is not None) or "torch" in sys.modules:
+            import torch
+            return int(torch.cuda.current_stream(self.ekf.device).cuda_stream)
+        return 0
+
+    def _view(self):
+        v = QleDeviceView()
+        v.struct_size = C.sizeof(QleDeviceView)
+        check(lib().qle_get_device_view(self.ekf._h, C.byref(v)))
+        return v
+
+    def _inputs_view(self, t):
+        if self._seq is None:
+            self._seq = self.ekf.make_inputs(2, [0, 1])
+        iv = QleInputsView()
+        iv.struct_size = C.sizeof(QleInputsView)
+        check(lib().qle_inputs_get_device_view(self._seq._h, t, C.byref(iv)))
+        return iv
+
+    # ---- one tick from device tensors
+    def tick(self, u, z=None, mask=None):
+        """One filter tick: u [B,6] and, on a tick with tag poses, z [B,7] and mask [B] (uint8 / bool; None = all), what
+        `step(u, z, mask)` means on the host path (with `enable_gating`: what `filter_update` means).  Asynchronous; the
+        tensors may be reused as soon as the call returns (the caller's current stream is ordered behind the pack)."""
+        B = self.ekf.batch
+        src = self._check(u, "u", (B, 6), _FLOATS)
+        if z is not None and self._check(z, "z", (B, 7), _FLOATS) != src:
+            raise ValueError("u and z must have the same dtype")
+        if mask is not None:
+            if z is None:
+                raise ValueError("mask given without z")
+            self._check_mask(mask, B)
+        D = devio_lib()
+        view = self._view()
+        t = 0 if z is None else 1
+        iv = self._inputs_view(t)
+        stream = self._current_stream(u, z, mask)
+        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
+        _dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), u.data_ptr(), None if z is None else z.data_ptr(),
+                                  None if mask is None else mask.data_ptr(), _FLOATS[src]))
+        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        check(lib().qle_run(self.ekf._h, self._seq._h, t, 1))
+
+    def _check_mask(self, mask, B):
+        for attr in ("data_ptr", "dtype", "shape", "device"):
+            if not hasattr(mask, attr):
+                raise ValueError(f"mask: expected a device tensor, got {type(mask).__name__}")
+        kind, idx = _device_index(mask)
+        if kind not in ("cuda", "hip") or idx != self.ekf.device:
+            raise ValueError(f"mask: tensor is on {mask.device}, the filter handle is on GPU {self.ekf.device}")
+        if _dtype_name(mask) not in _MASKS:
+            raise ValueError(f"mask: dtype {mask.dtype} not supported, expected uint8 or bool")
+        if tuple(mask.shape) != (B,):
+            raise ValueError(f"mask: expected shape {(B,)}, got {tuple(mask.shape)}")
+        if hasattr(mask, "is_contiguous") and not mask.is_contiguous():
+            raise ValueError("mask: tensor must be contiguous")
+
+    # ---- outputs as device tensors
+    def _out_dtype(self, dtype):
+        if dtype is None:
+            return "float32" if self._float == QDV_F32 else "float64"
+        dn = str(dtype).rsplit(".", 1)[-1]
+        if dn not in _FLOATS:
+            raise ValueError(f"dtype {dtype} not supported, expected float32 or float64")
+        return dn
+
+    def _alloc(self, shapes, dn):
+        import torch
+        dev = torch.device("cuda", self.ekf.device)
+        return [torch.empty(s, dtype=getattr(torch, dn), device=dev) for s in shapes]
+
+    def state(self, dtype=None, out=None):
+        """(x [B,16], P [B,n,n]) as device tensors: `get_state()` without the host.  out = (x, P) fills given tensors."""
+        B, n = self.ekf.batch, self.ekf.num_states
+        if out is None:
+            dn = self._out_dtype(dtype)
+            x, P = self._alloc([(B, 16), (B, n, n)], dn)
+        else:
+            x, P = out
+            dn = self._check(x, "x", (B, 16), _FLOATS)
+            if self._check(P, "P", (B, n, n), _FLOATS) != dn or (dtype is not None and self._out_dtype(dtype) != dn):
+                raise ValueError("x, P and dtype must agree")
+        D = devio_lib()
+        view = self._view()
+        stream = self._current_stream(x, P)
+        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
+        _dcheck(D.qdv_unpack_state(C.byref(view), x.data_ptr(), P.data_ptr(), _FLOATS[dn]))
+        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        return x, P
+
+    _REPORT = (("pose", (7,)), ("pose_cov", (6, 6)), ("vel", (3,)), ("bias", (6,)))
+
+    def report(self, dtype=None, out=None):
+        """What the node publishes after a tick (relative_pose_EKF_node.cpp:192-220) as device tensors: the dict of
+        `BatchedRelativePoseEKF.report()`.  out = a dict with any of its keys fills those tensors only."""
+        B = self.ekf.batch
+        if out is None:
+            dn = self._out_dtype(dtype)
+            out = dict(zip((k for k, _ in self._REPORT), self._alloc([(B,) + s for _, s in self._REPORT], dn)))
+        else:
+            if not out or set(out) - {k for k, _ in self._REPORT}:
+                raise ValueError(f"out: expected a dict with keys among {[k for k, _ in self._REPORT]}")
+            dns = {self._check(out[k], k, (B,) + s, _FLOATS) for k, s in self._REPORT if k in out}
+            if len(dns) != 1 or (dtype is not None and self._out_dtype(dtype) not in dns):
+                raise ValueError("the tensors of out and dtype must agree")
+            dn = dns.pop()
+        D = devio_lib()
+        view = self._view()
+        ptr = [out[k].data_ptr() if k in out else None for k, _ in self._REPORT]
+        stream = self._current_stream(*out.values())
+        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
+        _dcheck(D.qdv_unpack_report(C.byref(view), ptr[0], ptr[1], ptr[2], ptr[3], _FLOATS[dn]))
+        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        return out
+
+    def close(self):
+        if self._seq is not None:
+            self._seq.close()
+            self._seq = None

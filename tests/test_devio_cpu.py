@@ -1,0 +1,303 @@
+"""CPU tests of the device-tensor boundary (include/qle_devio.h, libqle_devio.so, quadrotor_landing_amd/devio.py): the library
+builds, exports and binds what its header declares, its structs have the sizes the binding assumes, its generated code passes
+the stale-EXEC audit, its kernels are its own (none shared with, none added to, libqle_ekf.so), it links the HIP runtime only,
+the kernels' index arithmetic -- compiled for the host under ASan/UBSan -- agrees with an independent restatement of the
+published layout on every word of a ragged batch, and DeviceIO refuses bad tensors before any GPU call."""
+import ctypes as C
+import os
+import re
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import test_variant_table_cpu as tv
+from quadrotor_landing_amd import _lib, devio
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
+HEADER = os.path.join(ROOT, "include", "qle_devio.h")
+CLANGXX = "/opt/rocm/lib/llvm/bin/clang++"
+B_RAGGED = 2391   # the variant table's ragged size: 37 whole tiles and one of 23 filters
+
+
+@pytest.fixture(scope="module")
+def devio_so():
+    if not os.path.exists(devio.DEVIO_LIB_PATH):
+        subprocess.run(["make", "-C", CSRC, "../libqle_devio.so"], check=True)
+    return devio.DEVIO_LIB_PATH
+
+
+def test_library_exports_and_binds_every_declared_function(devio_so):
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    names = sorted(set(re.findall(r"\b(qdv_[a-z0-9_]+)\s*\(", txt)))
+    assert len(names) >= 6
+    L = C.CDLL(devio_so)
+    for n in names:
+        assert hasattr(L, n), f"{n} declared in include/qle_devio.h but not exported"
+    assert sorted(devio.SYMBOLS) == names
+    assert devio.devio_lib() is not None
+
+
+def test_view_struct_sizes_match_the_header(tmp_path):
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "qle_devio.h"\n'
+                   'int main(void) { printf("%zu %zu %zu %zu %zu\\n", sizeof(qle_device_view), sizeof(qle_inputs_view), offsetof(qle_device_view, struct_size),'
+                   ' offsetof(qle_device_view, state), offsetof(qle_device_view, ab_static)); return 0; }\n')
+    exe = tmp_path / "sz"
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    V = _lib.QleDeviceView
+    assert got == [C.sizeof(V), C.sizeof(_lib.QleInputsView), V.struct_size.offset, V.state.offset, V.ab_static.offset]
+    assert V.struct_size.offset == 0 and _lib.QleInputsView.struct_size.offset == 0
+
+
+def test_generated_device_code_passes_the_stale_exec_audit(devio_so):
+    r = subprocess.run(["make", "-C", CSRC, "audit-devio"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    m = re.search(r"audit-devio: no register copy under a stale EXEC in (\d+) kernels", r.stdout)
+    assert m and int(m.group(1)) >= 1, r.stdout[-2000:]
+
+
+def _kernels(path):
+    d = open(path, "rb").read()
+    kds = []
+    for co in tv._gfx950_code_objects(d):
+        kds += [s[:-3] for s in tv._symbols(co, 2) if s.endswith(".kd")]
+    return set(kds)
+
+
+def test_kernels_are_disjoint_from_the_tick_library(devio_so):
+    mine, main = _kernels(devio_so), _kernels(_lib.LIB_PATH)
+    assert mine and main
+    assert not mine & main, sorted(mine & main)
+    ids = {_lib.demangle(m) for m in mine}
+    assert all(i.startswith("void qdv::k_dv_") for i in ids), sorted(ids)
+    assert not any("qdv::" in _lib.demangle(m) for m in main)
+    # the three kernel families of the boundary, every dtype pair of each
+    fam = {i.split("<")[0].split("::")[1] for i in ids}
+    assert fam == {"k_dv_pack", "k_dv_state", "k_dv_report"}, fam
+
+
+def _needed(path):
+    d = open(path, "rb").read()
+    secs = tv._sections(d)
+    dyn = [s for s in secs if s[0] == ".dynamic"][0]
+    strtab = secs[dyn[6]][4]
+    out = []
+    for o in range(dyn[4], dyn[4] + dyn[5], 16):
+        tag, val = struct.unpack_from("<qQ", d, o)
+        if tag == 0:
+            break
+        if tag == 1:   # DT_NEEDED
+            out.append(d[strtab + val:d.index(b"\0", strtab + val)].decode())
+    return out
+
+
+def test_library_links_the_hip_runtime_only(devio_so):
+    needed = _needed(devio_so)
+    assert any(n.startswith("libamdhip64") for n in needed), needed
+    assert not any("qle_ekf" in n or "oracle" in n for n in needed), needed
+
+
+# ---------------------------------------------------------------- the index map, two ways
+def np_off(w, i, WT, VW):
+    """off(w, i) = (i/64) WT 64 + ((w/VW) 64 + i%64) VW + w%VW; a record whose length is not a multiple of VW
+    ends in one row of the remaining words per filter."""
+    w = np.asarray(w)[:, None]; i = np.asarray(i)[None, :]
+    nf = WT // VW
+    full = (i // 64) * WT * 64 + ((w // VW) * 64 + i % 64) * VW + w % VW
+    rem = WT - nf * VW
+    tail = (i // 64) * WT * 64 + nf * VW * 64 + (i % 64) * rem + (w - nf * VW)
+    return np.where(w < nf * VW, full, tail)
+
+
+def np_sidx(i, k):
+    """Order of the 120 covariance words (ekf_device.hpp): 5 x 5 blocks of 3 x 3, block-row after block-row;
+    quad-lane l holds column l of every block (b, c), c > b, and two entries of each diagonal block; memory quad 3m + l is
+    the m-th quad of lane l."""
+    i, k = min(i, k), max(i, k)
+    base = [0, 14, 25, 33, 38]
+    b, c, ii, kk = i // 3, k // 3, i % 3, k % 3
+    if b < c:
+        lane, pos = kk, base[b] + 2 + 3 * (c - b - 1) + ii
+    elif ii == kk:
+        lane, pos = kk, base[b]
+    else:
+        lane, pos = {(0, 1): 1, (1, 2): 2, (0, 2): 0}[(ii, kk)], base[b] + 1
+    return 4 * (3 * (pos // 4) + lane) + pos % 4
+
+
+def np_p_word(a, b, compact):
+    a, b = min(a, b), max(a, b)
+    if compact:   # the 9 x 9 pose block as its own row-major triangle in record words 16..60
+        return 16 + a * 9 - a * (a - 1) // 2 + (b - a) if b < 9 else -1
+    return 16 + np_sidx(a, b)
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    """tests/cpp/devio_index_harness.cpp built for the host with ASan + UBSan and run on the ragged batch."""
+    d = tmp_path_factory.mktemp("dvh")
+    exe, out = str(d / "dvh"), str(d / "dvh.bin")
+    subprocess.run([CLANGXX, "-O1", "-g", "-std=c++17", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-Wall", "-Wno-unknown-pragmas",
+                    "-Wno-unused-function", "-Wno-unused-variable", "-Wno-pass-failed", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-o", exe, os.path.join(ROOT, "tests", "cpp", "devio_index_harness.cpp")], check=True)
+    r = subprocess.run([exe, str(B_RAGGED), out], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]   # a sanitizer report ends the program with a non-zero status
+    data = np.fromfile(out, dtype=np.int64)
+    assert data.size == int(r.stdout.split()[0])
+    return data
+
+
+class _Reader:
+    def __init__(self, a):
+        self.a, self.p = a, 0
+
+    def take(self, n):
+        v = self.a[self.p:self.p + n]
+        assert v.size == n
+        self.p += n
+        return v
+
+
+def test_index_arithmetic_agrees_with_the_published_layout(harness):
+    B = B_RAGGED
+    rd = _Reader(harness)
+    idx = np.arange(B)
+    # 1. off(w, i) for every word and filter, both dtypes, every record size
+    for VW in (4, 2):
+        for WT in (6, 8, 24, 144):
+            got = rd.take(WT * B).reshape(WT, B)
+            ref = np_off(np.arange(WT), idx, WT, VW)
+            np.testing.assert_array_equal(got, ref, err_msg=f"off(w, i), VW={VW}, WT={WT}")
+            assert ref.max() < -(-B // 64) * 64 * WT and len(np.unique(ref)) == ref.size
+            # the words of a quad row are contiguous: what lets a lane move them as one 16-byte access
+            nf = WT // VW
+            for k in range(nf):
+                np.testing.assert_array_equal(np.diff(got[k * VW:(k + 1) * VW], axis=0), 1)
+                assert (got[k * VW] * (16 // VW) % 16 == 0).all()
+    # 2. p_word
+    pairs = [(a, b) for a in range(15) for b in range(a, 15)]
+    for c in (0, 1):
+        got = rd.take(120)
+        np.testing.assert_array_equal(got, [np_p_word(a, b, c) for a, b in pairs], err_msg=f"p_word, compact={c}")
+    full = sorted(np_p_word(a, b, 0) for a, b in pairs)
+    assert full == list(range(16, 136))
+    # 3. the full n x n covariance
+    for n, c in ((15, 0), (9, 0), (9, 1)):
+        got = rd.take(n * n).reshape(n, n)
+        ref = np.array([[np_p_word(a, b, c) for b in range(n)] for a in range(n)])
+        np.testing.assert_array_equal(got, ref, err_msg=f"covariance map n={n} compact={c}")
+        np.testing.assert_array_equal(got, got.T)
+        assert (got >= 16).all() and got.max() < (64 if c else 136)
+    # 4. the report: NODE.cpp:203-210 takes rows / columns {0-2, 6-8} of P
+    sel = [0, 1, 2, 6, 7, 8]
+    slots = [rd.take(136) for _ in (0, 1)]
+    pose, cov, vel, bias = rd.take(7), rd.take(36).reshape(6, 6), rd.take(3), rd.take(6)
+    for c in (0, 1):
+        s = slots[c]
+        np.testing.assert_array_equal(s[:16], np.arange(16))
+        for a in range(6):
+            for b in range(6):
+                rw = np_p_word(sel[a], sel[b], c)
+                assert s[rw] == cov[a, b] and 16 <= cov[a, b] < 37, (c, a, b)
+        assert (s[16:] >= 0).sum() == 21 and len(set(s[s >= 16])) == 21
+    np.testing.assert_array_equal(pose, [0, 1, 2, 6, 7, 8, 9])
+    np.testing.assert_array_equal(vel, [3, 4, 5])
+    np.testing.assert_array_equal(bias, [10, 11, 12, 13, 14, 15])
+    # 5. odd pitches: the 64 lanes' "word w of my filter" accesses fall on distinct banks (32 lanes per LDS cycle, 4-byte words on
+    #    64 banks for fp32; 8-byte words as bank pairs for fp64)
+    pitches = rd.take(5)
+    for p in pitches:
+        assert p % 2 == 1
+        for half in (np.arange(32), np.arange(32, 64)):
+            assert len(set((half * p) % 64)) == 32 and len(set((2 * half * p) % 64)) == 32
+    # 6. the AoS side: every word below B * W moved exactly once, by the right (filter, word), nothing at or beyond (ASan), and
+    #    all but the pieces across the ragged end as whole 16-byte pieces
+    walks = [(6, 7), (7, 7), (16, 17), (225, 121), (81, 121), (7, 37), (36, 37), (3, 37), (6, 37)]
+    for V in (4, 2):
+        for W, pitch in walks:
+            cnt, fw = rd.take(B * W), rd.take(B * W)
+            lds_max, vec, scalar = rd.take(3)
+            assert (cnt == 1).all(), (W, V)
+            q = np.arange(B * W)
+            np.testing.assert_array_equal(fw, ((q // W) % 64) * 1000 + q % W, err_msg=f"W={W} V={V}")
+            assert vec * V + scalar == B * W and scalar < V
+            if W < pitch:
+                assert lds_max == 63 * pitch + W - 1   # inside the 64 * pitch words of the LDS image
+    assert rd.p == harness.size
+
+
+# ---------------------------------------------------------------- DeviceIO argument checks (no GPU call is reached)
+class FakeTensor:
+    def __init__(self, shape, dtype="float32", device="cuda:0", contiguous=True, ptr=0x7F0000000000):
+        self.shape, self.dtype, self.device, self._c, self._p = tuple(shape), dtype, device, contiguous, ptr
+
+    def data_ptr(self):
+        return self._p
+
+    def is_contiguous(self):
+        return self._c
+
+
+class FakeEkf:
+    batch, dtype, device, num_states = 100, _lib.QLE_F32, 0, 15
+    _h = None
+
+
+def test_deviceio_refuses_bad_tensors_before_any_gpu_call(monkeypatch):
+    def boom(*a, **k):
+        raise AssertionError("a native library was reached")
+    monkeypatch.setattr(devio, "devio_lib", boom)
+    monkeypatch.setattr(devio, "lib", boom)
+    io = devio.DeviceIO(FakeEkf())
+    B = 100
+    good_u = FakeTensor((B, 6))
+    bad = [
+        dict(u=np.zeros((B, 6), np.float32)),                                  # a host array: no data_ptr / device
+        dict(u=FakeTensor((B, 6), device="cuda:1")),                           # another GPU
+        dict(u=FakeTensor((B, 6), device="cpu")),
+        dict(u=FakeTensor((B, 6), dtype="float16")),
+        dict(u=FakeTensor((B, 7))),
+        dict(u=FakeTensor((B + 1, 6))),
+        dict(u=FakeTensor((B, 6), contiguous=False)),
+        dict(u=FakeTensor((B, 6), ptr=0x7F0000000008)),                        # not 16-byte aligned
+        dict(u=good_u, z=FakeTensor((B, 6))),
+        dict(u=good_u, z=FakeTensor((B, 7), dtype="float64")),                 # u and z of different dtypes
+        dict(u=good_u, z=FakeTensor((B, 7)), mask=FakeTensor((B,), dtype="float32")),
+        dict(u=good_u, z=FakeTensor((B, 7)), mask=FakeTensor((B, 1), dtype="uint8")),
+        dict(u=good_u, z=FakeTensor((B, 7)), mask=FakeTensor((B,), dtype="bool", device="cuda:3")),
+        dict(u=good_u, mask=FakeTensor((B,), dtype="uint8")),                   # a mask without z
+    ]
+    for kw in bad:
+        with pytest.raises(ValueError):
+            io.tick(**kw)
+    with pytest.raises(ValueError):
+        io.state(out=(FakeTensor((B, 16)), FakeTensor((B, 9, 9))))
+    with pytest.raises(ValueError):
+        io.state(out=(FakeTensor((B, 16)), FakeTensor((B, 15, 15), dtype="float64")))
+    with pytest.raises(ValueError):
+        io.state(dtype="int32")
+    with pytest.raises(ValueError):
+        io.report(out={"pose": FakeTensor((B, 6))})
+    with pytest.raises(ValueError):
+        io.report(out={"nonsense": FakeTensor((B, 7))})
+    with pytest.raises(ValueError):
+        io.report(out={"pose": FakeTensor((B, 7)), "vel": FakeTensor((B, 3), dtype="float64")})
+    # torch-style dtype and device objects are read the same way
+    class Dev:
+        type, index = "cuda", 0
+    with pytest.raises(AssertionError, match="native library"):
+        io.tick(FakeTensor((B, 6), dtype="torch.float32", device=Dev()))
+
+
+def test_product_imports_without_torch():
+    code = ("import sys; sys.modules['torch'] = None\n"
+            "import quadrotor_landing_amd as qla\n"
+            "from quadrotor_landing_amd import devio\n"
+            "assert qla.DeviceIO is devio.DeviceIO and devio.devio_lib() is not None and qla.lib() is not None\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
