@@ -179,8 +179,9 @@ int qle_step(qle_batch *h, const double *u, const double *z, const uint8_t *mask
  * 16.81 and 22.46 are its 0.99 and 0.999 quantiles).  A filter with mask 0 or without state (qle_initialize_state_masked)
  * gets nu = 0, S = 0, NIS = NaN and is never accepted; so is a filter whose S is not positive definite (NIS = NaN).
  * The gated calls are the single-rate filter without the device decision logic: with multirate_ekf set or
- * qle_enable_gating on they return QLE_ERR_STATE.  Follow-ups, not provided: a gate inside the multirate replay, a gate
- * inside the decision logic of qle_filter_update, and a fused single-launch gated tick (qle_step_gated is three launches). */
+ * qle_enable_gating on they return QLE_ERR_STATE.  qle_step_gated is three launches and stays so; the gate as ONE launch in
+ * front of the fused tick, fed from GPU memory and working alongside qle_enable_gating, is include/qle_gate.h
+ * (libqle_gate.so).  Follow-up, not provided: a gate inside the multirate replay. */
 /* delta_y (EKF.cpp:447-450), S = G P G^T + R_k (EKF.cpp:475) and NIS of tag pose z = [batch][7]
  * against the current state, where mask != 0 (NULL = all).  Reads the state, changes nothing.
  * nu = [batch][6], S = [batch][36] (symmetric, row-major), nis = [batch]; any output may be NULL

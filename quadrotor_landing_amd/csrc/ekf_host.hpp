@@ -22,6 +22,7 @@
 
 #include "ekf_gate.hpp"
 #include "ekf_layout.hpp"
+#include "ekf_params.hpp"
 
 using namespace qle;
 
@@ -132,21 +133,6 @@ struct qle_inputs {
 static constexpr int64_t kStageFilters = 32768;
 static constexpr int64_t kStageDoubles = kStageFilters * 225;
 
-template <typename T> static DevParams<T> make_dev(const qle_params& p, const qle_derived& d)
-{
-    DevParams<T> o;
-    o.dT = (T)d.dT_nom;
-    o.dTw = p.est_bias ? (T)d.dT_nom : T(0);
-    o.bias_on = p.est_bias ? T(1) : T(0);
-    o.small_ang_tol = (T)p.small_ang_tol;
-    for (int i = 0; i < 3; ++i) { o.g[i] = (T)p.g[i]; o.r_v_cv[i] = (T)p.r_v_cv[i]; o.ab_static[i] = (T)p.ab_static[i]; o.wb_static[i] = (T)p.wb_static[i]; }
-    for (int i = 0; i < 4; ++i) o.q_vc[i] = (T)d.q_vc[i];
-    for (int i = 0; i < 9; ++i) o.C_vc[i] = (T)d.C_vc[i];
-    for (int i = 0; i < 12; ++i) o.Q[i] = (T)d.Q[i];
-    for (int i = 0; i < 6; ++i) o.R[i] = (T)d.R[i];
-    o.compact = 0;   // set by qle_set_params
-    return o;
-}
 template <typename T> static const DevParams<T>& dev(const qle_batch* h);
 template <> const DevParams<float>& dev<float>(const qle_batch* h) { return h->pf; }
 template <> const DevParams<double>& dev<double>(const qle_batch* h) { return h->pd; }

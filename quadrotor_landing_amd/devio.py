@@ -9,14 +9,19 @@ between the handle's stream and the caller's current stream (include/qle_devio.h
 A tensor is a torch tensor or anything with `data_ptr()`, `dtype`, `shape`, `device` (and optionally `is_contiguous()`).
 torch is imported lazily: only to find the caller's current stream for torch tensors and to allocate outputs.
 
-Still host-fed through `BatchedRelativePoseEKF`: seeding (`initialize_state`), `set_state`, the per-filter stamps of
-`dynamic_meas_delay` (`filter_update(t_curr=..., apriltag_time=...)`) and the NIS-gated calls.
+The chi-square gate runs from device tensors too: `tick(u, z, mask, chi2_max=...)` puts one read-only kernel (gate.py,
+libqle_gate.so) in front of the unchanged tick, and `innovation(z)` returns nu, S and NIS as device tensors.  The host-array
+`step_gated` / `update_gated` of `BatchedRelativePoseEKF` stay as they are (three launches per gated tick).
+
+Still host-fed through `BatchedRelativePoseEKF`: seeding (`initialize_state`), `set_state` and the per-filter stamps of
+`dynamic_meas_delay` (`filter_update(t_curr=..., apriltag_time=...)`).
 """
 import ctypes as C
 import os
 import sys
 
-from ._lib import QLE_F32, QleDeviceView, QleInputsView, QleError, check, lib
+from . import gate as _gate
+from ._lib import QLE_ERR_STATE, QLE_F32, QleDeviceView, QleInputsView, QleError, check, lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEVIO_LIB_PATH = os.environ.get("QLE_DEVIO_LIB") or os.path.join(_HERE, "libqle_devio.so")
@@ -87,6 +92,7 @@ class DeviceIO:
         self.ekf = ekf
         self._float = QDV_F32 if ekf.dtype == QLE_F32 else QDV_F64
         self._seq = None   # two ticks: 0 without a tag slot, 1 with one (made on the first tick)
+        self._zero_u = {}  # innovation(): an all-zero IMU tensor per source dtype for the pack
 
     # ---- argument checks (before any GPU call)
     def _check(self, t, name, shape, dtypes):
@@ -129,10 +135,18 @@ class DeviceIO:
         return iv
 
     # ---- one tick from device tensors
-    def tick(self, u, z=None, mask=None):
+    def tick(self, u, z=None, mask=None, chi2_max=None, return_nis=False):
         """One filter tick: u [B,6] and, on a tick with tag poses, z [B,7] and mask [B] (uint8 / bool; None = all), what
         `step(u, z, mask)` means on the host path (with `enable_gating`: what `filter_update` means).  Asynchronous; the
-        tensors may be reused as soon as the call returns (the caller's current stream is ordered behind the pack)."""
+        tensors may be reused as soon as the call returns (the caller's current stream is ordered behind the pack).
+
+        chi2_max (> 0; inf accepts every finite NIS): a chi-square gate in front of the tick.  One more launch (k_pregate) between
+        the pack and the tick evaluates NIS = delta_y^T S^-1 delta_y of every tag pose against the predicted state and clears the
+        mask where it exceeds chi2_max; the unchanged tick then applies exactly the accepted corrections (with `enable_gating`:
+        a rejected tag pose is no detection -- not consumed, no reset of the rate limiter).  Returns `accepted` [B] (uint8) as a
+        device tensor; with return_nis=True returns (accepted, nis [B], nu [B,6], S [B,6,6]) in the handle's compute dtype.  A
+        masked or uninitialised filter, or one whose S is not positive definite: not accepted, NIS = NaN.  Refused with
+        multirate_ekf."""
         B = self.ekf.batch
         src = self._check(u, "u", (B, 6), _FLOATS)
         if z is not None and self._check(z, "z", (B, 7), _FLOATS) != src:
@@ -141,16 +155,74 @@ class DeviceIO:
             if z is None:
                 raise ValueError("mask given without z")
             self._check_mask(mask, B)
+        if chi2_max is None:
+            if return_nis:
+                raise ValueError("return_nis given without chi2_max")
+        else:
+            chi2_max = self._check_gate(z, chi2_max)
         D = devio_lib()
         view = self._view()
         t = 0 if z is None else 1
         iv = self._inputs_view(t)
         stream = self._current_stream(u, z, mask)
+        out = None
+        if chi2_max is not None:
+            G = _gate.gate_lib()
+            dn = self._out_dtype(None)
+            accepted = self._alloc([(B,)], "uint8")[0]
+            out = [accepted] + (self._alloc([(B,), (B, 6), (B, 6, 6)], dn) if return_nis else [None, None, None])
         _dcheck(D.qdv_wait_stream(C.byref(view), stream))
         _dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), u.data_ptr(), None if z is None else z.data_ptr(),
                                   None if mask is None else mask.data_ptr(), _FLOATS[src]))
+        if out is not None:
+            ptr = [None if o is None else o.data_ptr() for o in out]
+            _gate.gcheck(G.qgt_gate_tick(C.byref(view), C.byref(iv), C.byref(self.ekf.params), chi2_max, ptr[1], ptr[0], ptr[2], ptr[3],
+                                         _FLOATS[dn]))
         _dcheck(D.qdv_signal_stream(C.byref(view), stream))
         check(lib().qle_run(self.ekf._h, self._seq._h, t, 1))
+        if out is not None:
+            return tuple(out) if return_nis else out[0]
+
+    def _check_gate(self, z, chi2_max):
+        """The gate's own refusals (before any GPU call): a tick without tag poses, a threshold that is not > 0, multirate_ekf."""
+        if z is None:
+            raise ValueError("chi2_max given on a tick without tag poses (z is None)")
+        chi2_max = float(chi2_max)
+        if not chi2_max > 0.0:
+            raise ValueError(f"chi2_max must be > 0 (got {chi2_max})")
+        self._refuse_multirate()
+        return chi2_max
+
+    def _refuse_multirate(self):
+        if self.ekf.params.multirate_ekf:
+            raise QleError(QLE_ERR_STATE, "the gate does not support multirate_ekf: a delayed measurement's innovation belongs to a history entry")
+
+    def innovation(self, z, mask=None, dtype=None):
+        """(nu [B,6], S [B,6,6], nis [B]) of tag poses z [B,7] against the stored state as device tensors: `innovation(z, mask)` of the
+        host path without the host.  Changes nothing.  Filters with mask 0 or without state: nu = 0, S = 0, nis = NaN.
+        (The pack always moves an IMU record, so an all-zero one is kept per source dtype; a pack entry that takes u = NULL is a
+        follow-up for include/qle_devio.h.)"""
+        B = self.ekf.batch
+        src = self._check(z, "z", (B, 7), _FLOATS)
+        if mask is not None:
+            self._check_mask(mask, B)
+        dn = self._out_dtype(dtype)
+        self._refuse_multirate()
+        D, G = devio_lib(), _gate.gate_lib()
+        view = self._view()
+        iv = self._inputs_view(1)
+        if self._zero_u.get(src) is None:   # the pack moves an IMU record too; the slot is private and every tick packs its own
+            import torch
+            self._zero_u[src] = torch.zeros((B, 6), dtype=getattr(torch, src), device=torch.device("cuda", self.ekf.device))
+        nu, S, nis = self._alloc([(B, 6), (B, 6, 6), (B,)], dn)
+        stream = self._current_stream(z, mask)
+        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
+        _dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), self._zero_u[src].data_ptr(), z.data_ptr(),
+                                  None if mask is None else mask.data_ptr(), _FLOATS[src]))
+        _gate.gcheck(G.qgt_innovation(C.byref(view), C.byref(iv), C.byref(self.ekf.params), nis.data_ptr(), nu.data_ptr(), S.data_ptr(),
+                                      _FLOATS[dn]))
+        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        return nu, S, nis
 
     def _check_mask(self, mask, B):
         for attr in ("data_ptr", "dtype", "shape", "device"):
