@@ -13,6 +13,10 @@ The chi-square gate runs from device tensors too: `tick(u, z, mask, chi2_max=...
 libqle_gate.so) in front of the unchanged tick, and `innovation(z)` returns nu, S and NIS as device tensors.  The host-array
 `step_gated` / `update_gated` of `BatchedRelativePoseEKF` stay as they are (three launches per gated tick).
 
+Filter consistency against a truth that lives on the GPU: `nees(x_true, ...)` returns every filter's normalised estimation error
+squared e^T P^-1 e and an eight-double batch summary as device tensors (consistency.py, libqle_consistency.so: two read-only kernels,
+no synchronisation).
+
 Still host-fed through `BatchedRelativePoseEKF`: seeding (`initialize_state`), `set_state` and the per-filter stamps of
 `dynamic_meas_delay` (`filter_update(t_curr=..., apriltag_time=...)`).
 """
@@ -20,6 +24,7 @@ import ctypes as C
 import os
 import sys
 
+from . import consistency as _cons
 from . import gate as _gate
 from ._lib import QLE_ERR_STATE, QLE_F32, QleDeviceView, QleInputsView, QleError, check, lib
 
@@ -223,6 +228,37 @@ class DeviceIO:
                                       _FLOATS[dn]))
         _dcheck(D.qdv_signal_stream(C.byref(view), stream))
         return nu, S, nis
+
+    # ---- filter consistency against a truth
+    def nees(self, x_true, mask=None, blocks="all", chi2_hi=float("inf"), return_err=False, dtype=None):
+        """NEES = e^T P^-1 e of every filter against x_true [B,16] (r, v, q xyzw, ab, wb: the layout of the state, with the total true
+        biases; float32 or float64), e = truth minus estimate in the filter's error-state convention (include/qle_consistency.h).
+        blocks: the marginal NEES is taken over -- "all", names such as "pose" (= r + theta), "r", "r+theta+ab+wb", or the bit mask
+        (bit 0 r, 1 v, 2 theta, 3 ab, 4 wb); dof = 3 x the number of blocks.  mask [B] (uint8 / bool; None = all).
+        Returns (nees [B], summary) or, with return_err=True, (nees, err [B,n], summary) as device tensors; summary is 8 float64
+        values in the order of consistency.SUMMARY_FIELDS (count, sum_nees, sum_nees_sq, n_above = count with nees > chi2_hi,
+        n_not_pd, sum_r_err_sq, sum_theta_err_sq, dof).  Asynchronous, no synchronisation, deterministic; changes nothing.  A filter
+        with mask 0 or without state: nees = NaN, err = 0, not counted; a covariance that is not positive definite: nees = NaN,
+        counted in n_not_pd."""
+        B, n = self.ekf.batch, self.ekf.num_states
+        src = self._check(x_true, "x_true", (B, 16), _FLOATS)
+        if mask is not None:
+            self._check_mask(mask, B)
+        bits = _cons.block_mask(blocks, n)
+        chi2_hi = _cons.check_chi2_hi(chi2_hi)
+        dn = self._out_dtype(dtype)
+        D, K = devio_lib(), _cons.consistency_lib()
+        view = self._view()
+        nees = self._alloc([(B,)], dn)[0]
+        err = self._alloc([(B, n)], dn)[0] if return_err else None
+        summary = self._alloc([(8,)], "float64")[0]
+        stream = self._current_stream(x_true, mask)
+        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
+        _cons.ccheck(K.qcs_nees(C.byref(view), C.byref(self.ekf.params), x_true.data_ptr(), _FLOATS[src],
+                                None if mask is None else mask.data_ptr(), bits, chi2_hi, nees.data_ptr(),
+                                None if err is None else err.data_ptr(), summary.data_ptr(), _FLOATS[dn]))
+        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        return (nees, err, summary) if return_err else (nees, summary)
 
     def _check_mask(self, mask, B):
         for attr in ("data_ptr", "dtype", "shape", "device"):

@@ -289,6 +289,51 @@ class BatchedRelativePoseEKF:
         check(lib().qle_synth_rmse(self._h, inputs._h, _dp(out)))
         return out
 
+    # ---- filter consistency against a truth (include/qle_consistency.h)
+    def _device_view(self):
+        from ._lib import QleDeviceView
+        v = QleDeviceView()
+        v.struct_size = C.sizeof(QleDeviceView)
+        check(lib().qle_get_device_view(self._h, C.byref(v)))
+        return v
+
+    def nees(self, x_true, mask=None, blocks="all", chi2_hi=float("inf")):
+        """Normalised estimation error squared e^T P^-1 e of every filter against the truth x_true [B,16] (r, v, q xyzw, ab, wb: the
+        layout of the state, with the total true biases), e = truth minus estimate in the filter's error-state convention, over all
+        states or the marginal of `blocks` ("all", "pose", "r", "r+theta+ab+wb", ... or the bit mask of include/qle_consistency.h).
+        Host arrays in and out; the arithmetic runs on the device (k_nees), the state is unchanged.  Returns a dict: nees [B]
+        (NaN for a filter with mask 0, without state, or with a covariance that is not positive definite), err [B,n] and the fields
+        of the batch summary (consistency.SUMMARY_FIELDS) with mean_nees = sum_nees / count added."""
+        from . import consistency as cs
+        B, n = self.batch, self.num_states
+        xt = _f64(x_true, (B, 16))
+        m = _u8(mask, (B,))
+        bits = cs.block_mask(blocks, n)
+        chi2_hi = cs.check_chi2_hi(chi2_hi)
+        K = cs.consistency_lib()
+        view = self._device_view()
+        nees = np.empty(B); err = np.empty((B, n)); s = cs.QcsSummary()
+        cs.ccheck(K.qcs_nees_host(C.byref(view), C.byref(self.params), _dp(xt), None if m is None else m.ctypes.data_as(_pu8), bits, chi2_hi,
+                                  _dp(nees), _dp(err), C.byref(s)))
+        out = {"nees": nees, "err": err}
+        out.update({k: float(getattr(s, k)) for k in cs.SUMMARY_FIELDS})
+        out["mean_nees"] = out["sum_nees"] / out["count"] if out["count"] > 0 else float("nan")
+        return out
+
+    def synth_nees(self, inputs, chi2_hi=float("inf")):
+        """nees() against the generator's truth at the end of `inputs` (synth_truth: pose and IMU bias; the generator keeps no
+        velocity, so the velocity block is left out): blocks r, theta, ab, wb, or r, theta for a filter without bias states.
+        The generator's bias truth is the unknown part of the IMU bias; the total true bias adds the static (known) biases, per filter
+        where per-filter parameters are in force."""
+        pose, bias = self.synth_truth(inputs)
+        if self._device_view().filter_params:
+            static = self.get_filter_params()[:, 12:18]
+        else:
+            static = np.array(list(self.params.ab_static) + list(self.params.wb_static))[None, :]
+        xt = np.zeros((self.batch, 16))
+        xt[:, 0:3] = pose[:, 0:3]; xt[:, 6:10] = pose[:, 3:7]; xt[:, 10:16] = bias + static
+        return self.nees(xt, blocks="r+theta+ab+wb" if self.num_states == 15 else "r+theta", chi2_hi=chi2_hi)
+
     # ---- reporting / control
     def report(self):
         """What the node publishes after a tick (relative_pose_EKF_node.cpp:192-220)."""
