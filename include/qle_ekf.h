@@ -152,6 +152,11 @@ int qle_initialize_state(qle_batch *h, const double *z, int32_t reinit_bias);
  * untouched -- no predict, no counter, no history entry -- and a filter seeded later starts with
  * upds_since_correction = 0 (EKF.cpp:77) and a one-entry history (EKF.cpp:337-339). */
 int qle_initialize_state_masked(qle_batch *h, const double *z, const uint8_t *mask, int32_t reinit_bias);
+/* qle_initialize_state_masked (EKF.cpp:305-344) with the tag poses and the mask taken from the tag slot of tick t of a
+ * device-resident sequence (z 7 words + mask word per filter, as qle_inputs_upload_tick / qdv_pack_inputs write them)
+ * instead of host arrays.  Asynchronous, no host copy.  Tick t without a tag slot: QLE_ERR_INVALID; so are inputs that
+ * belong to another handle (or batch size), refused before any launch. */
+int qle_initialize_state_slot(qle_batch *h, const qle_inputs *in, int64_t t, int32_t reinit_bias);
 /* state_initialized (EKF.hpp:125) of every filter: [batch]. */
 int qle_get_state_initialized(qle_batch *h, uint8_t *state_initialized);
 /* Side outputs of the last tick: accel_rel (EKF.hpp:49; [batch][3]) and the

@@ -7,3 +7,4 @@ from .devio import DeviceIO  # noqa: F401
 from .params import default_params, derive, load_yaml, make_params, set_fields  # noqa: F401
 from . import replay  # noqa: F401
 from . import consistency  # noqa: F401
+from . import health  # noqa: F401

@@ -109,6 +109,7 @@ SYMBOLS = {
     "qle_get_state": (C.c_int, [_vp, _pd, _pd]),
     "qle_initialize_state": (C.c_int, [_vp, _pd, _i32]),
     "qle_initialize_state_masked": (C.c_int, [_vp, _pd, _pu8, _i32]),
+    "qle_initialize_state_slot": (C.c_int, [_vp, _vp, _i64, _i32]),
     "qle_get_state_initialized": (C.c_int, [_vp, _pu8]),
     "qle_enable_aux": (C.c_int, [_vp, _i32]),
     "qle_get_aux": (C.c_int, [_vp, _pd, _pd]),

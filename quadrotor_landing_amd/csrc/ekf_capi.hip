@@ -924,11 +924,11 @@ extern "C" int qle_get_tick_flags(qle_batch* h, uint8_t* performed_correction, u
 }
 
 template <typename T>
-static int seed_t(qle_batch* h, int reinit)
+static int seed_t(qle_batch* h, const void* zs, int reinit)
 {
     const qle_derived& d = h->der;
     QLE_TRY(mr_prepare(h));   // a pending whole-batch history restart first; the seeded filters then restart theirs
-    return launch(h, k_seed<T>, grid_for(h, 256), dim3(256), 0, dev<T>(h), (const T*)h->tick_z, (T*)state_cur(h), (T)d.cov_init[0], (T)d.cov_init[3],
+    return launch(h, k_seed<T>, grid_for(h, 256), dim3(256), 0, dev<T>(h), (const T*)zs, (T*)state_cur(h), (T)d.cov_init[0], (T)d.cov_init[3],
                   (T)d.cov_init[6], (T)d.cov_init[9], (T)d.cov_init[12], reinit, (int32_t)h->tick, h->last_corr, h->mr ? h->hist_first : (int32_t*)nullptr,
                   h->mr ? (T*)h->mr_anchor : (T*)nullptr, h->B);
 }
@@ -937,7 +937,7 @@ extern "C" int qle_initialize_state_masked(qle_batch* h, const double* z, const 
     QLE_TRY(check_handle(h));
     if (!z) return fail(QLE_ERR_INVALID, "z is null");
     QLE_TRY(BY_DTYPE(h, pack_z, h, z, mask, h->tick_z));
-    QLE_TRY(BY_DTYPE(h, seed_t, h, reinit_bias));
+    QLE_TRY(BY_DTYPE(h, seed_t, h, h->tick_z, reinit_bias));
     h->state_set = true;
     return QLE_OK;
 }
@@ -1123,6 +1123,18 @@ extern "C" int qle_run(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n
     return QLE_OK;
 }
 
+// qle_initialize_state_masked from the tag slot of tick t of a device-resident sequence: k_seed reads the slot instead of h->tick_z.
+extern "C" int qle_initialize_state_slot(qle_batch* h, const qle_inputs* in, int64_t t, int32_t reinit_bias)
+{
+    QLE_TRY(check_handle(h));
+    if (!in || in->h != h) return fail(QLE_ERR_INVALID, "inputs do not belong to this handle (another handle or batch size)");
+    QLE_TRY(check_tick(in, t));
+    const int32_t s = in->slot[(size_t)t];
+    if (s < 0) return fail(QLE_ERR_INVALID, "tick %lld has no measurement slot to seed from", (long long)t);
+    QLE_TRY(BY_DTYPE(h, seed_t, h, z_at(in, s), reinit_bias));
+    h->state_set = true;
+    return QLE_OK;
+}
 
 // ---- device views (include/qle_ekf.h): where the records live, for a device-side boundary.  Host code only, read-only.
 extern "C" int qle_get_device_view(qle_batch* h, qle_device_view* out)
@@ -1235,7 +1247,7 @@ extern "C" int qle_synth_generate(qle_batch* h, qle_inputs* in, const qle_synth_
     if (!c) return fail(QLE_ERR_INVALID, "cfg is null");
     QLE_TRY(BY_DTYPE(h, synth_t, h, in, c));
     // seed every filter from the generator's first (pre-sequence) tag pose, left in tick_z
-    QLE_TRY(BY_DTYPE(h, seed_t, h, 1));
+    QLE_TRY(BY_DTYPE(h, seed_t, h, h->tick_z, 1));
     h->state_set = true;
     return QLE_OK;
 }

@@ -48,6 +48,31 @@ __host__ __device__ constexpr int nees_dof(uint32_t blocks)
     return n;
 }
 
+// P = L D L^T of the leading N x N block, in place on the packed words (the pivots d_m are left on the diagonal).  RHS: y = L^-1 y is
+// carried along and the quadratic form sum y_m^2 / d_m returned (0 without).  Returns in pd whether every pivot is > 0 (a NaN pivot is
+// not).  The one factorisation of the read-only diagnostics: k_nees (nees_eval below) and k_health (ekf_health.hpp) both call it.
+template <typename T, int N, bool RHS>
+__device__ __forceinline__ T ldl_factor(T (&P)[120], T (&y)[N], bool& pd)
+{
+    T quad = T(0);
+    pd = true;
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        const T d = P[sidx(c, c)];
+        pd = pd && d > T(0);
+        const T inv = T(1) / d;
+#pragma unroll
+        for (int j = c + 1; j < N; ++j) {
+            const T l = P[sidx(c, j)] * inv;
+#pragma unroll
+            for (int j2 = j; j2 < N; ++j2) P[sidx(j, j2)] -= l * P[sidx(c, j2)];
+            if constexpr (RHS) y[j] -= l * y[c];
+        }
+        if constexpr (RHS) quad += y[c] * y[c] * inv;
+    }
+    return quad;
+}
+
 // e = truth (-) estimate (15 words: r, v, th, ab, wb) of state x against truth row xt (r, v, q xyzw, ab, wb; the TOTAL biases) and the
 // returned NEES over the blocks selected.  P: the 15-state register image of the packed covariance, factored in place (destroyed).
 // COMPACT: the bias blocks are not held (zero) and never selected -- the factor runs over the 9 pose states only.
@@ -94,28 +119,14 @@ __device__ __forceinline__ T nees_eval(const T (&x)[16], T (&P)[120], const T (&
         }
     }
     // P = L D L^T in place, y = L^-1 e carried along: NEES = sum y_m^2 / d_m
-    T nees = T(0);
-    pd = true;
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        const T d = P[sidx(c, c)];
-        pd = pd && d > T(0);
-        const T inv = T(1) / d;
-#pragma unroll
-        for (int j = c + 1; j < N; ++j) {
-            const T l = P[sidx(c, j)] * inv;
-#pragma unroll
-            for (int j2 = j; j2 < N; ++j2) P[sidx(j, j2)] -= l * P[sidx(c, j2)];
-            y[j] -= l * y[c];
-        }
-        nees += y[c] * y[c] * inv;
-    }
+    const T nees = ldl_factor<T, N, true>(P, y, pd);
     return pd ? nees : T(NAN);
 }
 
 }  // namespace qle
 
-#if defined(__HIPCC__)
+// (ekf_health.hpp takes ldl_factor from this header and none of its kernels: QLE_CONSISTENCY_NO_KERNELS)
+#if defined(__HIPCC__) && !defined(QLE_CONSISTENCY_NO_KERNELS)
 #include "ekf_layout.hpp"
 #include "ekf_pregate.hpp"   // load_rec_cached, put
 
@@ -214,4 +225,4 @@ __global__ __launch_bounds__(kBlock) void k_nees_reduce(const double* __restrict
 }
 
 }  // namespace qle
-#endif  // __HIPCC__
+#endif  // __HIPCC__ && !QLE_CONSISTENCY_NO_KERNELS

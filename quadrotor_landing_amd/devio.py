@@ -17,8 +17,13 @@ Filter consistency against a truth that lives on the GPU: `nees(x_true, ...)` re
 squared e^T P^-1 e and an eight-double batch summary as device tensors (consistency.py, libqle_consistency.so: two read-only kernels,
 no synchronisation).
 
-Still host-fed through `BatchedRelativePoseEKF`: seeding (`initialize_state`), `set_state` and the per-filter stamps of
-`dynamic_meas_delay` (`filter_update(t_curr=..., apriltag_time=...)`).
+Filter lifecycle from device tensors (health.py, libqle_health.so, and qle_initialize_state_slot of the tick library):
+`seed(z, mask)` seeds filters from tag poses on the GPU, `health(...)` classifies every filter in one read-only launch (non-finite,
+not positive definite, quaternion norm, sigma limits), `retire(mask)` makes filters "uninitialised" so that ticks skip them, and
+`reseed(z, mask)` seeds the flagged filters that have a detection.  No host copy, no synchronisation; multirate handles included.
+
+Still host-fed through `BatchedRelativePoseEKF`: `set_state` and the per-filter stamps of `dynamic_meas_delay`
+(`filter_update(t_curr=..., apriltag_time=...)`).
 """
 import ctypes as C
 import os
@@ -26,6 +31,7 @@ import sys
 
 from . import consistency as _cons
 from . import gate as _gate
+from . import health as _health
 from ._lib import QLE_ERR_STATE, QLE_F32, QleDeviceView, QleInputsView, QleError, check, lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -216,13 +222,11 @@ class DeviceIO:
         D, G = devio_lib(), _gate.gate_lib()
         view = self._view()
         iv = self._inputs_view(1)
-        if self._zero_u.get(src) is None:   # the pack moves an IMU record too; the slot is private and every tick packs its own
-            import torch
-            self._zero_u[src] = torch.zeros((B, 6), dtype=getattr(torch, src), device=torch.device("cuda", self.ekf.device))
+        zero_u = self._zeros_u(src)
         nu, S, nis = self._alloc([(B, 6), (B, 6, 6), (B,)], dn)
         stream = self._current_stream(z, mask)
         _dcheck(D.qdv_wait_stream(C.byref(view), stream))
-        _dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), self._zero_u[src].data_ptr(), z.data_ptr(),
+        _dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), zero_u.data_ptr(), z.data_ptr(),
                                   None if mask is None else mask.data_ptr(), _FLOATS[src]))
         _gate.gcheck(G.qgt_innovation(C.byref(view), C.byref(iv), C.byref(self.ekf.params), nis.data_ptr(), nu.data_ptr(), S.data_ptr(),
                                       _FLOATS[dn]))
@@ -259,6 +263,104 @@ class DeviceIO:
                                 None if err is None else err.data_ptr(), summary.data_ptr(), _FLOATS[dn]))
         _dcheck(D.qdv_signal_stream(C.byref(view), stream))
         return (nees, err, summary) if return_err else (nees, summary)
+
+    def _zeros_u(self, src):
+        """The pack always moves an IMU record too: an all-zero one per source dtype (the slot is private and every tick packs its own)."""
+        if self._zero_u.get(src) is None:
+            import torch
+            self._zero_u[src] = torch.zeros((self.ekf.batch, 6), dtype=getattr(torch, src), device=torch.device("cuda", self.ekf.device))
+        return self._zero_u[src]
+
+    # ---- filter lifecycle: seed, health check, retire, reseed
+    def seed(self, z, mask=None, reinit_bias=False):
+        """`initialize_state(z, reinit_bias, mask)` of the host path from device tensors: seeds the filters with mask != 0 (None = all)
+        from their tag poses z [B,7] (float32 or float64), bit for bit what `qle_initialize_state_masked` writes for the same values.
+        Works on a handle that was never seeded from the host.  Asynchronous; the tensors may be reused as soon as the call returns."""
+        B = self.ekf.batch
+        src = self._check(z, "z", (B, 7), _FLOATS)
+        if mask is not None:
+            self._check_mask(mask, B)
+        D = devio_lib()
+        view = self._view()
+        iv = self._inputs_view(1)
+        zero_u = self._zeros_u(src)
+        stream = self._current_stream(z, mask)
+        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
+        self._seed_from_slot(D, view, iv, zero_u, z, mask, src, reinit_bias)
+        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+
+    def _seed_from_slot(self, D, view, iv, zero_u, z, mask, src, reinit_bias):
+        _dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), zero_u.data_ptr(), z.data_ptr(), None if mask is None else mask.data_ptr(),
+                                  _FLOATS[src]))
+        check(lib().qle_initialize_state_slot(self.ekf._h, self._seq._h, 1, int(bool(reinit_bias))))
+
+    def health(self, mask=None, sigma_r_max=float("inf"), sigma_v_max=float("inf"), sigma_theta_max=float("inf"), qnorm_tol=1e-3,
+               select=None, return_summary=False):
+        """Classify every filter in one read-only launch.  Returns (status, flagged), uint8 device tensors [B], or with
+        return_summary=True (status, flagged, summary) with the nine float64 counts of health.SUMMARY_FIELDS (evaluated, flagged,
+        uninitialised, then one count per status bit) as a device tensor.  status holds the bits of health.BITS for an initialised
+        filter with mask != 0 (None = all) and 0 otherwise: NONFINITE (any record word NaN or Inf; nothing else is evaluated then),
+        NOT_PD (a pivot of the L D L^T of P is <= 0), QNORM (|q.q - 1| > qnorm_tol), SIGMA_R / SIGMA_V / SIGMA_THETA (the largest
+        variance of the block is above the limit squared; inf = no limit).  flagged = (status & select) != 0, select: None (every
+        bit), names such as "nonfinite+not_pd", or the bit mask.  `flagged` is a mask for `retire`.  Asynchronous, no
+        synchronisation, deterministic; changes nothing."""
+        B = self.ekf.batch
+        if mask is not None:
+            self._check_mask(mask, B)
+        lim = _health.make_limits(sigma_r_max, sigma_v_max, sigma_theta_max, qnorm_tol, select)
+        D, H = devio_lib(), _health.health_lib()
+        view = self._view()
+        status, flagged = self._alloc([(B,), (B,)], "uint8")
+        summary = self._alloc([(len(_health.SUMMARY_FIELDS),)], "float64")[0] if return_summary else None
+        stream = self._current_stream(mask)
+        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
+        _health.hcheck(H.qhl_health(C.byref(view), C.byref(lim), None if mask is None else mask.data_ptr(), status.data_ptr(),
+                                    flagged.data_ptr(), None if summary is None else summary.data_ptr()))
+        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        return (status, flagged, summary) if return_summary else (status, flagged)
+
+    def retire(self, mask):
+        """The filters with mask != 0 lose their state: they become "uninitialised" (their record is zeroed), every tick leaves them
+        untouched and a later `seed` treats them as fresh (upds_since_correction = 0, a one-entry multirate history).  One launch,
+        asynchronous."""
+        self._check_mask(mask, self.ekf.batch)
+        D, H = devio_lib(), _health.health_lib()
+        view = self._view()
+        stream = self._current_stream(mask)
+        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
+        _health.hcheck(H.qhl_retire(C.byref(view), mask.data_ptr()))
+        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+
+    def reseed(self, z, mask=None, reinit_bias=True, **limits):
+        """Health check, then seed the flagged filters that have a detection: `health(**limits)` over every filter, reseeded =
+        flagged AND mask (mask: the filters z holds a tag pose for; None = all), `seed(z, reseeded, reinit_bias)`.  Returns
+        (status, reseeded), uint8 device tensors.  A flagged filter without a detection stays as it is (and stays flagged):
+        `retire` it to keep it out of the ticks.
+
+        reinit_bias defaults to True here, unlike `seed`: seeding keeps the bias words of x unless asked to zero them
+        (relative_pose_EKF.cpp:317-321), so a NaN bias -- the usual company of a diverged filter -- would survive the reseed and
+        break the filter again on its next tick."""
+        B = self.ekf.batch
+        src = self._check(z, "z", (B, 7), _FLOATS)
+        if mask is not None:
+            self._check_mask(mask, B)
+        unknown = set(limits) - {"sigma_r_max", "sigma_v_max", "sigma_theta_max", "qnorm_tol", "select"}
+        if unknown:
+            raise ValueError(f"reseed: unknown limits {sorted(unknown)}")
+        lim = _health.make_limits(**limits)
+        D, H = devio_lib(), _health.health_lib()
+        view = self._view()
+        iv = self._inputs_view(1)
+        zero_u = self._zeros_u(src)
+        status, reseeded = self._alloc([(B,), (B,)], "uint8")
+        stream = self._current_stream(z, mask)
+        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
+        _health.hcheck(H.qhl_health(C.byref(view), C.byref(lim), None, status.data_ptr(), reseeded.data_ptr(), None))
+        if mask is not None:
+            _health.hcheck(H.qhl_and_masks(C.byref(view), reseeded.data_ptr(), mask.data_ptr(), reseeded.data_ptr()))
+        self._seed_from_slot(D, view, iv, zero_u, z, reseeded, src, reinit_bias)
+        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        return status, reseeded
 
     def _check_mask(self, mask, B):
         for attr in ("data_ptr", "dtype", "shape", "device"):

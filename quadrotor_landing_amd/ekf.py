@@ -334,6 +334,24 @@ class BatchedRelativePoseEKF:
         xt[:, 0:3] = pose[:, 0:3]; xt[:, 6:10] = pose[:, 3:7]; xt[:, 10:16] = bias + static
         return self.nees(xt, blocks="r+theta+ab+wb" if self.num_states == 15 else "r+theta", chi2_hi=chi2_hi)
 
+    # ---- filter health
+    def health(self, mask=None, sigma_r_max=float("inf"), sigma_v_max=float("inf"), sigma_theta_max=float("inf"), qnorm_tol=1e-3, select=None):
+        """Which filters are broken?  Host arrays in and out; the classification runs on the device (k_health), the state is unchanged.
+        Returns a dict: status [B] (uint8, the bits of health.BITS; 0 for a filter with mask 0 or without state), flagged [B]
+        (bool: status & select) and the counts of the batch summary (health.SUMMARY_FIELDS).  Arguments: `DeviceIO.health`."""
+        from . import health as hl
+        B = self.batch
+        m = _u8(mask, (B,))
+        lim = hl.make_limits(sigma_r_max, sigma_v_max, sigma_theta_max, qnorm_tol, select)
+        H = hl.health_lib()
+        view = self._device_view()
+        status = np.zeros(B, np.uint8); flagged = np.zeros(B, np.uint8); s = hl.QhlSummary()
+        hl.hcheck(H.qhl_health_host(C.byref(view), C.byref(lim), None if m is None else m.ctypes.data_as(_pu8), status.ctypes.data_as(_pu8),
+                                    flagged.ctypes.data_as(_pu8), C.byref(s)))
+        out = {"status": status, "flagged": flagged.astype(bool)}
+        out.update({k: int(getattr(s, k)) for k in hl.SUMMARY_FIELDS})
+        return out
+
     # ---- reporting / control
     def report(self):
         """What the node publishes after a tick (relative_pose_EKF_node.cpp:192-220)."""

@@ -1,0 +1,294 @@
+"""CPU tests of the filter lifecycle (include/qle_health.h, libqle_health.so, quadrotor_landing_amd/health.py, csrc/ekf_health.hpp, and
+qle_initialize_state_slot of the tick library): the library builds, exports and binds what its header declares, its kernels are its own
+(none shared with, none added to, the four existing libraries), its generated code passes the stale-EXEC audit and uses no scratch
+memory, every refusal is made before any GPU call (without a GPU a HIP call would fail with another error class), and the per-filter
+classification of k_health -- health_classify, compiled for the host with g++ -- gives the status bytes of a numpy restatement.
+
+Reference: health_util.py.  Every comparison is exact: a status byte is right or wrong.  What the host build does not cover are the
+kernel's loads, its masks and its batch summary: tests/test_gpu_lifecycle.py.
+"""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import health_util as hu
+import test_variant_table_cpu as tv
+from quadrotor_landing_amd import _lib, consistency, devio, gate, health
+from test_devio_cpu import FakeTensor, _kernels, _needed
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
+HEADER = os.path.join(ROOT, "include", "qle_health.h")
+N_KERNELS = 10   # k_health: T x {compact, full n = 9, full n = 15}; k_health_reduce; k_retire: T; k_and_masks
+
+
+@pytest.fixture(scope="module")
+def health_so():
+    if not os.path.exists(health.HEALTH_LIB_PATH):
+        subprocess.run(["make", "-C", CSRC, "../libqle_health.so"], check=True)
+    return health.HEALTH_LIB_PATH
+
+
+def test_library_exports_and_binds_every_declared_function(health_so):
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    names = sorted(set(re.findall(r"\b(qhl_[a-z0-9_]+)\s*\(", txt)))
+    assert names == ["qhl_and_masks", "qhl_health", "qhl_health_host", "qhl_last_error", "qhl_launch_count", "qhl_retire"]
+    L = health.health_lib()
+    for n in names:
+        assert hasattr(L, n), f"{n} declared in include/qle_health.h but not exported"
+    assert sorted(health.SYMBOLS) == names
+    d = open(health_so, "rb").read()
+    exported = {s for s in tv._symbols(d, 11) if s.startswith("qhl_")}   # SHT_DYNSYM
+    assert exported == set(names), sorted(exported ^ set(names))
+
+
+def test_seed_from_a_slot_is_exported_from_the_tick_library():
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "qle_ekf.h")).read(), flags=re.S)
+    assert re.search(r"int qle_initialize_state_slot\(qle_batch \*h, const qle_inputs \*in, int64_t t, int32_t reinit_bias\);", txt)
+    L = C.CDLL(_lib.LIB_PATH)
+    assert hasattr(L, "qle_initialize_state_slot") and "qle_initialize_state_slot" in _lib.SYMBOLS
+    # refusals that need no GPU: a null handle, and (before any launch) nothing else can be reached without one
+    fn = _lib.lib().qle_initialize_state_slot
+    assert fn(None, None, 0, 0) == _lib.QLE_ERR_INVALID
+
+
+def test_summary_struct_is_nine_doubles_in_the_header_order():
+    txt = open(HEADER).read()
+    body = re.search(r"typedef struct qhl_summary \{(.*?)\} qhl_summary;", txt, flags=re.S).group(1)
+    fields = re.findall(r"double\s+([a-z_]+);", body)
+    assert tuple(fields) == health.SUMMARY_FIELDS and len(fields) == 9 and C.sizeof(health.QhlSummary) == 72
+    body = re.search(r"typedef struct qhl_limits \{(.*?)\} qhl_limits;", txt, flags=re.S).group(1)
+    assert re.findall(r"(?:uint32_t|double)\s+([a-z_]+);", body) == [n for n, _ in health.QhlLimits._fields_]
+    for name, bit in health.BITS.items():
+        assert re.search(rf"#define QHL_{name.upper()} {bit}u", txt), name
+    assert health.ALL == sum(health.BITS.values()) == 63
+    assert (hu.NONFINITE, hu.NOT_PD, hu.QNORM, hu.SIGMA_R, hu.SIGMA_V, hu.SIGMA_THETA) == tuple(health.BITS.values())
+
+
+def test_kernels_are_disjoint_from_the_four_existing_libraries(health_so):
+    mine = _kernels(health_so)
+    others = {p: _kernels(p) for p in (_lib.LIB_PATH, devio.DEVIO_LIB_PATH, gate.GATE_LIB_PATH, consistency.CONSISTENCY_LIB_PATH)}
+    assert mine and all(others.values())
+    fams = ("k_health", "k_retire", "k_and_masks")
+    for p, k in others.items():
+        assert not mine & k, (p, sorted(mine & k))
+        assert not any(f in _lib.demangle(m) for m in k for f in fams), p
+    ids = {_lib.demangle(m) for m in mine}
+    assert all(i.startswith(("void qle::k_health<", "qle::k_health_reduce(", "void qle::k_retire<", "qle::k_and_masks(")) for i in ids), sorted(ids)
+    assert len(ids) == N_KERNELS
+
+
+def test_library_links_the_hip_runtime_only(health_so):
+    needed = _needed(health_so)
+    assert any(n.startswith("libamdhip64") for n in needed), needed
+    assert not any("qle_" in n or "oracle" in n for n in needed), needed
+
+
+@pytest.fixture(scope="module")
+def audit(health_so):
+    r = subprocess.run(["make", "-C", CSRC, "audit-health"], capture_output=True, text=True, timeout=900)
+    return r, os.path.join(CSRC, "build", "asm", "health_capi.s")
+
+
+def test_generated_device_code_passes_the_stale_exec_audit(audit):
+    r, _ = audit
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    m = re.search(r"audit-health: no register copy under a stale EXEC in (\d+) kernels", r.stdout)
+    assert m and int(m.group(1)) == N_KERNELS, r.stdout[-2000:]
+
+
+def test_no_kernel_uses_scratch_memory(audit):
+    """The kernel descriptors of the generated assembly: 0 bytes of private segment for every kernel, no LDS for the per-filter part
+    (k_health_reduce alone keeps its 2 KiB of slices there), and the register counts the launch bounds promise -- fp32 within the 256
+    registers that leave room for two waves per SIMD."""
+    r, asm = audit
+    assert r.returncode == 0
+    txt = open(asm).read()
+    found = {}
+    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, flags=re.S):
+        name = _lib.demangle(m.group(1))
+        scratch = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", m.group(2)).group(1))
+        lds = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", m.group(2)).group(1))
+        vgpr = int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", m.group(2)).group(1))
+        found[name] = (scratch, lds, vgpr)
+    assert len([k for k in found if "k_health<" in k]) == 6 and len(found) == N_KERNELS, sorted(found)
+    for name, (scratch, lds, vgpr) in found.items():
+        print(f"{name.split('(')[0]}: scratch {scratch} B, LDS {lds} B, registers {vgpr}")
+        assert scratch == 0, (name, scratch)
+        assert lds == (2048 if "k_health_reduce" in name else 0), (name, lds)
+        assert vgpr <= (256 if "k_health<float" in name else 512), (name, vgpr)
+    assert all(re.search(r"\.private_segment_fixed_size:\s+0\b", s) for s in re.findall(r"\.private_segment_fixed_size:.*", txt))
+
+
+# ---------------------------------------------------------------- refusals, before any GPU call
+def _view(batch=100, dtype=_lib.QLE_F32, n=15):
+    v = _lib.QleDeviceView()
+    v.struct_size = C.sizeof(v); v.device = 0; v.dtype = dtype; v.num_states = n; v.batch = batch; v.padded_batch = -(-batch // 64) * 64
+    v.state = 0x7F0000000000; v.state_words = 144; v.record_words = 136
+    return v
+
+
+def test_library_refuses_before_any_gpu_call(health_so):
+    """No GPU here: a call that got as far as the HIP runtime would return QLE_ERR_HIP (or crash on the fake pointers), not these."""
+    H = health.health_lib()
+    v, lim = _view(), health.make_limits()
+    out = 0x7F3000000000
+    B = C.byref
+    INV = _lib.QLE_ERR_INVALID
+
+    def call(v_=B(v), l_=B(lim), mask=None, status=out, flagged=out + 4096, summ=out + 8192):
+        return H.qhl_health(v_, l_, mask, status, flagged, summ)
+
+    assert call(v_=None) == INV and b"view" in H.qhl_last_error()
+    assert call(l_=None) == INV and b"limits" in H.qhl_last_error()
+    short = _view(); short.struct_size = C.sizeof(short) - 8
+    assert call(v_=B(short)) == INV and b"struct_size" in H.qhl_last_error()
+    for size in (0, C.sizeof(lim) - 8, C.sizeof(lim) + 8):
+        bad = health.make_limits(); bad.struct_size = size
+        assert call(l_=B(bad)) == INV and b"struct_size" in H.qhl_last_error()
+    for select in (0, 64, 127, 1 << 8):
+        bad = health.make_limits(); bad.select = select
+        assert call(l_=B(bad)) == INV and b"select" in H.qhl_last_error()
+    for field in ("sigma_r_max", "sigma_v_max", "sigma_theta_max", "qnorm_tol"):
+        for val in (0.0, -1.0, float("nan"), float("-inf")):
+            bad = health.make_limits(); setattr(bad, field, val)
+            assert call(l_=B(bad)) == INV and field.encode() in H.qhl_last_error(), (field, val)
+    assert call(summ=out + 4) == INV and b"aligned" in H.qhl_last_error()
+    odd = _view(); odd.state = 0x7F0000000008
+    assert call(v_=B(odd)) == INV and b"aligned" in H.qhl_last_error()
+    for wrong in (dict(dtype=7), dict(n=12), dict(batch=0)):
+        assert call(v_=B(_view(**wrong))) == INV
+    # retire and the mask product
+    assert H.qhl_retire(None, out) == INV and H.qhl_retire(B(short), out) == INV
+    assert H.qhl_retire(B(v), None) == INV and b"mask" in H.qhl_last_error()
+    assert H.qhl_and_masks(B(v), None, out, out) == INV and H.qhl_and_masks(B(v), out, None, out) == INV
+    assert H.qhl_and_masks(B(v), out, out, None) == INV and H.qhl_and_masks(B(short), out, out, out) == INV
+    # the host entry refuses the same, before it allocates anything
+    st = np.zeros(100, np.uint8); s = health.QhlSummary()
+    p8 = st.ctypes.data_as(C.POINTER(C.c_uint8))
+    bad = health.make_limits(); bad.select = 0
+    assert H.qhl_health_host(B(v), B(bad), None, p8, None, B(s)) == INV and H.qhl_health_host(B(short), B(lim), None, p8, None, B(s)) == INV
+    assert H.qhl_health_host(None, B(lim), None, p8, None, B(s)) == INV
+    assert H.qhl_launch_count() == 0
+
+
+class FakeEkf:
+    batch, dtype, device, num_states = 100, _lib.QLE_F32, 0, 15
+    _h = None
+
+
+def test_deviceio_refuses_bad_lifecycle_arguments_before_any_gpu_call(monkeypatch):
+    def boom(*a, **k):
+        raise AssertionError("a native library was reached")
+    monkeypatch.setattr(devio, "devio_lib", boom)
+    monkeypatch.setattr(devio, "lib", boom)
+    monkeypatch.setattr(health, "health_lib", boom)
+    B = 100
+    io = devio.DeviceIO(FakeEkf())
+    z, m = FakeTensor((B, 7)), FakeTensor((B,), dtype="uint8")
+    bad_z = [np.zeros((B, 7)), FakeTensor((B, 6)), FakeTensor((B, 7), dtype="float16"), FakeTensor((B, 7), device="cuda:1"),
+             FakeTensor((B, 7), device="cpu"), FakeTensor((B, 7), contiguous=False), FakeTensor((B, 7), ptr=0x7F0000000008)]
+    bad_m = [np.zeros(B, np.uint8), FakeTensor((B,), dtype="float32"), FakeTensor((B, 1), dtype="uint8"), FakeTensor((B,), dtype="uint8", device="cuda:1"),
+             FakeTensor((B,), dtype="bool", contiguous=False)]
+    for t in bad_z:
+        with pytest.raises(ValueError):
+            io.seed(t)
+        with pytest.raises(ValueError):
+            io.reseed(t, m)
+    for t in bad_m:
+        with pytest.raises(ValueError):
+            io.seed(z, t)
+        with pytest.raises(ValueError):
+            io.health(mask=t)
+        with pytest.raises(ValueError):
+            io.retire(t)
+        with pytest.raises(ValueError):
+            io.reseed(z, t)
+    with pytest.raises((ValueError, AttributeError, TypeError)):
+        io.retire(None)
+    for kw in (dict(sigma_r_max=0.0), dict(sigma_v_max=-1.0), dict(sigma_theta_max=float("nan")), dict(qnorm_tol=0.0), dict(select=0),
+               dict(select=64), dict(select=""), dict(select="nonfinite+broken")):
+        with pytest.raises(ValueError):
+            io.health(**kw)
+        with pytest.raises(ValueError):
+            io.reseed(z, m, **kw)
+    with pytest.raises(ValueError, match="unknown limits"):
+        io.reseed(z, m, chi2_max=3.0)
+    for good in (lambda: io.seed(z, m), lambda: io.health(mask=m, sigma_r_max=2.0, select="nonfinite+not_pd"), lambda: io.retire(m),
+                 lambda: io.reseed(z, m, sigma_theta_max=0.5)):
+        with pytest.raises(AssertionError, match="native library"):
+            good()   # a good call is what reaches the libraries
+
+
+def test_select_names():
+    sm = health.select_mask
+    assert sm(None) == 63 and sm("all") == 63 and sm("nonfinite") == 1 and sm("nonfinite+not_pd") == 3 and sm(("qnorm", "sigma_r")) == 12
+    assert sm("sigma_v, sigma_theta") == 48 and sm(5) == 5
+    lim = health.make_limits(sigma_r_max=2.0, select="not_pd")
+    assert (lim.struct_size, lim.select, lim.sigma_r_max, lim.sigma_v_max, lim.qnorm_tol) == (C.sizeof(lim), 2, 2.0, float("inf"), 1e-3)
+
+
+# ---------------------------------------------------------------- the classification on the host
+SRC = os.path.join(ROOT, "tests", "cpp", "health_harness.cpp")
+GXX = ["g++", "-std=c++17", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
+       "-Wno-maybe-uninitialized", "-Wno-unused-but-set-variable"]
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    """tests/cpp/health_harness.cpp: ekf_health.hpp's health_classify compiled by g++ (the HIP headers define the device decorators
+    away), once as it is and once as a stand-alone program under AddressSanitizer and UBSan."""
+    d = tmp_path_factory.mktemp("hh")
+    plain, san = str(d / "health_harness"), str(d / "health_harness_san")
+    subprocess.run(GXX + ["-O2", "-o", plain, SRC], check=True)
+    subprocess.run(GXX + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", san, SRC], check=True)
+    return plain, san
+
+
+def run_harness(exe, tmp, dtype, n, compact, x, P, limits, select=63):
+    B = x.shape[0]
+    P15 = np.full((B, 15, 15), np.nan if compact else 0.0); P15[:, :n, :n] = P
+    if n == 9 and not compact:
+        P15[:, 9:, :] = 0.0; P15[:, :, 9:] = 0.0   # a full record of a filter without bias states holds zeros there
+    per = np.concatenate([x, P15.reshape(B, 225)], axis=1)
+    fin, fout = str(tmp / "in.bin"), str(tmp / "out.bin")
+    hdr = [B, int(dtype == "f64"), int(compact), n, limits["sigma_r_max"], limits["sigma_v_max"], limits["sigma_theta_max"], limits["qnorm_tol"], select]
+    with open(fin, "wb") as fh:
+        np.asarray(hdr, np.float64).tofile(fh); np.ascontiguousarray(per, np.float64).tofile(fh)
+    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
+    assert r.returncode == 0 and int(r.stdout) == B, (r.returncode, r.stdout, r.stderr[-3000:])
+    o = np.fromfile(fout, np.float64).reshape(B, 2)
+    return o[:, 0].astype(np.uint8), o[:, 1] != 0
+
+
+CASES = [("f64", 15, False), ("f64", 9, False), ("f64", 9, True), ("f32", 15, False), ("f32", 9, False), ("f32", 9, True)]
+
+
+@pytest.mark.parametrize("dtype,n,compact", CASES, ids=[f"{d}-n{n}-{'compact' if c else 'full'}" for d, n, c in CASES])
+def test_host_compiled_classification_matches_numpy(harness, tmp_path, dtype, n, compact):
+    x, P = hu.case_list(dtype, n)
+    ref, margin = hu.classify(x, P, **hu.LIMITS)
+    assert margin >= 0.5                                       # rounding cannot flip a positive-definite verdict
+    want = dict(zip(hu.CASE_NAMES, ref))
+    assert want == dict(healthy=0, nan_in_x=hu.NONFINITE, inf_in_P=hu.NONFINITE, indefinite=hu.NOT_PD, q_scaled=hu.QNORM, at_limit=0,
+                        above_limit=hu.SIGMA_R, no_state=0), want   # the list holds what it says
+    for exe in harness:                                        # the plain build, then the same file under ASan + UBSan
+        st, no_state = run_harness(exe, tmp_path, dtype, n, compact, x, P, hu.LIMITS)
+        print(f"{dtype} n={n} compact={compact}: status {list(st)} expected {list(ref)}")
+        assert np.array_equal(st, ref), (list(st), list(ref))
+        assert list(no_state) == [False] * 7 + [True]
+    # every bit at once, and limits that are off
+    x2, P2 = x.copy(), P.copy()
+    P2[3, 1, 1] = 5.0; P2[3, 4, 4] = 30.0; P2[3, 7, 7] = 10.0; x2[3, 6:10] = x[4, 6:10]
+    lims = dict(sigma_r_max=2.0, sigma_v_max=5.0, sigma_theta_max=3.0, qnorm_tol=1e-3)
+    ref2, margin2 = hu.classify(x2, P2, **lims)
+    assert margin2 >= 0.5 and ref2[3] == 62
+    st2, _ = run_harness(harness[0], tmp_path, dtype, n, compact, x2, P2, lims)
+    assert np.array_equal(st2, ref2), (list(st2), list(ref2))
+    off = dict(sigma_r_max=np.inf, sigma_v_max=np.inf, sigma_theta_max=np.inf, qnorm_tol=1e-3)
+    st3, _ = run_harness(harness[0], tmp_path, dtype, n, compact, x2, P2, off)
+    assert np.array_equal(st3, hu.classify(x2, P2, **off)[0]) and st3[3] == hu.NOT_PD | hu.QNORM and st3[6] == 0
