@@ -8,3 +8,4 @@ from .params import default_params, derive, load_yaml, make_params, set_fields  
 from . import replay  # noqa: F401
 from . import consistency  # noqa: F401
 from . import health  # noqa: F401
+from . import lookahead  # noqa: F401

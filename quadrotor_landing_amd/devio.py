@@ -22,6 +22,10 @@ Filter lifecycle from device tensors (health.py, libqle_health.so, and qle_initi
 not positive definite, quaternion norm, sigma limits), `retire(mask)` makes filters "uninitialised" so that ticks skip them, and
 `reseed(z, mask)` seeds the flagged filters that have a detection.  No host copy, no synchronisation; multirate handles included.
 
+Look-ahead (lookahead.py, libqle_lookahead.so): `lookahead(u, h)` returns a `Forecast` -- state and covariance h ticks ahead with the
+IMU sample held, computed in one read-only launch into a workspace of its own and readable through the same calls (`state`, `report`,
+`health`, `nees`, `lookahead` again), with the coast budget `ticks_to_limit` when a sigma limit is given.
+
 Still host-fed through `BatchedRelativePoseEKF`: `set_state` and the per-filter stamps of `dynamic_meas_delay`
 (`filter_update(t_curr=..., apriltag_time=...)`).
 """
@@ -32,6 +36,7 @@ import sys
 from . import consistency as _cons
 from . import gate as _gate
 from . import health as _health
+from . import lookahead as _look
 from ._lib import QLE_ERR_STATE, QLE_F32, QleDeviceView, QleInputsView, QleError, check, lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -361,6 +366,36 @@ class DeviceIO:
         self._seed_from_slot(D, view, iv, zero_u, z, reseeded, src, reinit_bias)
         _dcheck(D.qdv_signal_stream(C.byref(view), stream))
         return status, reseeded
+
+    # ---- look-ahead: state and covariance h ticks ahead, read-only
+    def lookahead(self, u, h, mask=None, sigma_r_max=float("inf"), sigma_theta_max=float("inf")):
+        """The forecast h ticks ahead (0 <= h <= lookahead.MAX_HORIZON) with the IMU sample u [B,6] (float32 or float64) held: what h
+        calls of `predict(u)` on a copy of the handle would leave, in ONE read-only launch -- the handle is not written.  Returns a
+        `lookahead.Forecast`: it owns the records and offers `state()`, `report()`, `health(...)`, `nees(x_true, ...)` and
+        `lookahead(u, h, ...)` on them.  Filters with mask 0 (uint8 / bool; None = all) or without state are skipped: their forecast
+        record is all zero ("uninitialised" to every consumer).  With sigma_r_max / sigma_theta_max (> 0; inf = no limit) the
+        forecast's `ticks_to_limit` [B] (int32 device tensor) is the smallest k in 0..h at which a position / attitude variance
+        exceeds its limit squared -- the tick at which `health` with these limits would first set SIGMA_R or SIGMA_THETA -- or -1
+        (none, or skipped).  Asynchronous, no synchronisation."""
+        B = self.ekf.batch
+        src = self._check(u, "u", (B, 6), _FLOATS)
+        h = _look.check_horizon(h)
+        if mask is not None:
+            self._check_mask(mask, B)
+        coast = _look.make_coast(sigma_r_max, sigma_theta_max)
+        D, K = devio_lib(), _look.lookahead_lib()
+        view = self._view()
+        nbytes = _look.kcheck(K.qlk_workspace_bytes(C.byref(view)))
+        workspace = self._alloc([(nbytes,)], "uint8")[0]
+        ticks = self._alloc([(B,)], "int32")[0] if coast is not None else None
+        ahead = QleDeviceView()
+        stream = self._current_stream(u, mask)
+        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
+        _look.kcheck(K.qlk_lookahead(C.byref(view), C.byref(self.ekf.params), u.data_ptr(), _FLOATS[src], h,
+                                     None if mask is None else mask.data_ptr(), workspace.data_ptr(), nbytes, C.byref(ahead),
+                                     None if coast is None else C.byref(coast), None if ticks is None else ticks.data_ptr()))
+        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        return _look.Forecast(self, ahead, workspace, h, ticks)
 
     def _check_mask(self, mask, B):
         for attr in ("data_ptr", "dtype", "shape", "device"):

@@ -352,6 +352,36 @@ class BatchedRelativePoseEKF:
         out.update({k: int(getattr(s, k)) for k in hl.SUMMARY_FIELDS})
         return out
 
+    # ---- look-ahead
+    def lookahead(self, u, h, mask=None, sigma_r_max=float("inf"), sigma_theta_max=float("inf")):
+        """State and covariance h ticks ahead with the IMU sample u [B,6] held: what h calls of `predict(u)` would leave, without
+        writing the handle (one launch of k_lookahead; arguments: `DeviceIO.lookahead`).  Host arrays in and out.  Returns
+        (x [B,16], P [B,n,n], ticks_to_limit [B] int32 or None when no limit is given); skipped filters: zero rows, -1."""
+        from . import devio as dv
+        from . import lookahead as lk
+        from ._lib import QleDeviceView
+        B, n = self.batch, self.num_states
+        uu = _f64(u, (B, 6))
+        h = lk.check_horizon(h)
+        m = _u8(mask, (B,))
+        coast = lk.make_coast(sigma_r_max, sigma_theta_max)
+        K, D = lk.lookahead_lib(), dv.devio_lib()
+        view = self._device_view()
+        nbytes = lk.kcheck(K.qlk_workspace_bytes(C.byref(view)))
+        import torch
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        ticks = np.empty(B, np.int32) if coast is not None else None
+        ahead = QleDeviceView()
+        lk.kcheck(K.qlk_lookahead_host(C.byref(view), C.byref(self.params), _dp(uu), h, None if m is None else m.ctypes.data_as(_pu8),
+                                       workspace.data_ptr(), nbytes, C.byref(ahead), None if coast is None else C.byref(coast),
+                                       None if ticks is None else ticks.ctypes.data_as(C.POINTER(C.c_int32))))
+        x = torch.empty((B, 16), dtype=torch.float64, device=workspace.device); P = torch.empty((B, n, n), dtype=torch.float64, device=workspace.device)
+        stream = int(torch.cuda.current_stream(self.device).cuda_stream)
+        dv._dcheck(D.qdv_wait_stream(C.byref(ahead), stream))
+        dv._dcheck(D.qdv_unpack_state(C.byref(ahead), x.data_ptr(), P.data_ptr(), dv.QDV_F64))
+        dv._dcheck(D.qdv_signal_stream(C.byref(ahead), stream))
+        return x.cpu().numpy(), P.cpu().numpy(), ticks
+
     # ---- reporting / control
     def report(self):
         """What the node publishes after a tick (relative_pose_EKF_node.cpp:192-220)."""
