@@ -174,6 +174,23 @@ def check(rc):
     return rc
 
 
+def load_side_library(path, symbols, what, needs_tick_library):
+    """Load one of the libraries beside libqle_ekf.so (devio, gate, consistency, health, lookahead) and bind `symbols`, name ->
+    (restype, argtypes); raises (never falls back) when it is missing.  needs_tick_library: the library takes qle_params_derive from
+    the tick library, which is loaded first so that it is the same copy the handle uses (QLE_LIB included)."""
+    if not os.path.exists(path):
+        raise ImportError(f"{path} not built: run `make -C quadrotor_landing_amd/csrc` (hipcc, gfx950). "
+                          f"There is no fallback for {what}.")
+    if needs_tick_library:
+        lib()
+    L = C.CDLL(path)
+    for name, (res, args) in symbols.items():
+        fn = getattr(L, name)  # AttributeError if the library does not export it
+        fn.restype = res
+        fn.argtypes = args
+    return L
+
+
 _cxa = None
 
 

@@ -8,7 +8,7 @@ Both kernels only read the handle.  `DeviceIO.nees` (devio.py) is the caller for
 import ctypes as C
 import os
 
-from ._lib import QleDeviceView, QleError, QleParams, lib
+from ._lib import QleDeviceView, QleError, QleParams, load_side_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CONSISTENCY_LIB_PATH = os.environ.get("QLE_CONSISTENCY_LIB") or os.path.join(_HERE, "libqle_consistency.so")
@@ -42,16 +42,7 @@ def consistency_lib():
     """Load libqle_consistency.so; raises (never falls back) when it is missing."""
     global _clib
     if _clib is None:
-        if not os.path.exists(CONSISTENCY_LIB_PATH):
-            raise ImportError(f"{CONSISTENCY_LIB_PATH} not built: run `make -C quadrotor_landing_amd/csrc` (hipcc, gfx950). "
-                              "There is no fallback for the consistency diagnostics.")
-        lib()   # libqle_consistency.so takes qle_params_derive from the tick library: the same copy the handle uses
-        L = C.CDLL(CONSISTENCY_LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _clib = L
+        _clib = load_side_library(CONSISTENCY_LIB_PATH, SYMBOLS, "the consistency diagnostics", needs_tick_library=True)
     return _clib
 
 

@@ -2,55 +2,19 @@
 // stream.  Works from the view structs of include/qle_ekf.h alone; links libamdhip64 only.
 #include "../../include/qle_devio.h"
 
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
-#include <cstdio>
 #include <mutex>
-#include <string>
 
 #include "devio_kernels.hpp"
+#include "side_host.hpp"
 
 using namespace qdv;
+using namespace qle::side;
 
-static thread_local std::string g_err;
+QLE_SIDE_LAST_ERROR(qdv_last_error)
 
-static int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-#define HIP_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(QLE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-#define QDV_TRY(expr)                  \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != QLE_OK) return rc_; \
-    } while (0)
-
-extern "C" const char* qdv_last_error(void) { return g_err.c_str(); }
-
-static int check_view(const qle_device_view* v)
-{
-    if (!v) return fail(QLE_ERR_INVALID, "view is null");
-    if (v->struct_size != sizeof(qle_device_view)) return fail(QLE_ERR_INVALID, "view: struct_size %u, this library was built for %zu", v->struct_size, sizeof(qle_device_view));
-    if (v->dtype != QLE_F32 && v->dtype != QLE_F64) return fail(QLE_ERR_INVALID, "view: dtype %d", v->dtype);
-    if (v->batch <= 0 || v->padded_batch != qle::padded_filters(v->batch)) return fail(QLE_ERR_INVALID, "view: batch %lld / padded %lld", (long long)v->batch, (long long)v->padded_batch);
-    if (!v->state || v->state_words != kSW) return fail(QLE_ERR_INVALID, "view: state records of %d words (this library: %d)", v->state_words, kSW);
-    if (v->num_states != 15 && v->num_states != 9) return fail(QLE_ERR_INVALID, "view: num_states %d", v->num_states);
-    if (v->compact && v->num_states != 9) return fail(QLE_ERR_INVALID, "view: compact records with num_states %d", v->num_states);
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(v->device));
-    return QLE_OK;
-}
+// This library takes a view of exactly its own size and does not ask for aligned records (include/qle_devio.h).  No GPU call: every
+// entry refuses what it refuses first and calls use_device() behind that.
+static int check_view(const qle_device_view* v) { return check_view(v, ViewSize::exact, false); }
 static int check_dtype(int32_t d, const char* what)
 {
     if (d != QDV_F32 && d != QDV_F64) return fail(QLE_ERR_INVALID, "%s must be QDV_F32 or QDV_F64 (got %d)", what, d);
@@ -61,8 +25,6 @@ static int check_aligned(const void* p, const char* what)
     if (((uintptr_t)p & 15u) != 0) return fail(QLE_ERR_INVALID, "%s is not 16-byte aligned", what);
     return QLE_OK;
 }
-static inline dim3 tiles(const qle_device_view* v) { return dim3((unsigned)(v->padded_batch / kTile)); }
-static inline hipStream_t stream_of(const qle_device_view* v) { return (hipStream_t)v->stream; }
 
 template <typename T, typename S>
 static int pack_t(const qle_device_view* v, const qle_inputs_view* in, const void* u, const void* z, const uint8_t* mask)
@@ -74,13 +36,14 @@ static int pack_t(const qle_device_view* v, const qle_inputs_view* in, const voi
 
 extern "C" int qdv_pack_inputs(const qle_device_view* view, const qle_inputs_view* in, const void* u, const void* z, const uint8_t* mask, int32_t src_dtype)
 {
-    QDV_TRY(check_view(view));
-    QDV_TRY(check_dtype(src_dtype, "src_dtype"));
+    QLE_TRY(check_view(view));
+    QLE_TRY(check_dtype(src_dtype, "src_dtype"));
     if (!in || in->struct_size != sizeof(qle_inputs_view) || !in->u) return fail(QLE_ERR_INVALID, "inputs view is null or of another size");
     if (!u) return fail(QLE_ERR_INVALID, "u is null");
     if (!in->z && (z || mask)) return fail(QLE_ERR_INVALID, "the tick has no tag slot but z or mask is given");
-    QDV_TRY(check_aligned(u, "u"));
-    QDV_TRY(check_aligned(z, "z"));
+    QLE_TRY(check_aligned(u, "u"));
+    QLE_TRY(check_aligned(z, "z"));
+    QLE_TRY(use_device(view));
     if (view->dtype == QLE_F32) return src_dtype == QDV_F32 ? pack_t<float, float>(view, in, u, z, mask) : pack_t<float, double>(view, in, u, z, mask);
     return src_dtype == QDV_F32 ? pack_t<double, float>(view, in, u, z, mask) : pack_t<double, double>(view, in, u, z, mask);
 }
@@ -96,11 +59,12 @@ static int state_t(const qle_device_view* v, void* x, void* P)
 
 extern "C" int qdv_unpack_state(const qle_device_view* view, void* x, void* P, int32_t dst_dtype)
 {
-    QDV_TRY(check_view(view));
-    QDV_TRY(check_dtype(dst_dtype, "dst_dtype"));
+    QLE_TRY(check_view(view));
+    QLE_TRY(check_dtype(dst_dtype, "dst_dtype"));
     if (!x && !P) return QLE_OK;
-    QDV_TRY(check_aligned(x, "x"));
-    QDV_TRY(check_aligned(P, "P"));
+    QLE_TRY(check_aligned(x, "x"));
+    QLE_TRY(check_aligned(P, "P"));
+    QLE_TRY(use_device(view));
     if (view->dtype == QLE_F32) return dst_dtype == QDV_F32 ? state_t<float, float>(view, x, P) : state_t<float, double>(view, x, P);
     return dst_dtype == QDV_F32 ? state_t<double, float>(view, x, P) : state_t<double, double>(view, x, P);
 }
@@ -118,13 +82,14 @@ static int report_t(const qle_device_view* v, void* pose, void* cov, void* vel, 
 
 extern "C" int qdv_unpack_report(const qle_device_view* view, void* pose, void* pose_cov, void* vel, void* bias, int32_t dst_dtype)
 {
-    QDV_TRY(check_view(view));
-    QDV_TRY(check_dtype(dst_dtype, "dst_dtype"));
+    QLE_TRY(check_view(view));
+    QLE_TRY(check_dtype(dst_dtype, "dst_dtype"));
     if (!pose && !pose_cov && !vel && !bias) return QLE_OK;
-    QDV_TRY(check_aligned(pose, "pose"));
-    QDV_TRY(check_aligned(pose_cov, "pose_cov"));
-    QDV_TRY(check_aligned(vel, "vel"));
-    QDV_TRY(check_aligned(bias, "bias"));
+    QLE_TRY(check_aligned(pose, "pose"));
+    QLE_TRY(check_aligned(pose_cov, "pose_cov"));
+    QLE_TRY(check_aligned(vel, "vel"));
+    QLE_TRY(check_aligned(bias, "bias"));
+    QLE_TRY(use_device(view));
     if (view->dtype == QLE_F32) return dst_dtype == QDV_F32 ? report_t<float, float>(view, pose, pose_cov, vel, bias) : report_t<float, double>(view, pose, pose_cov, vel, bias);
     return dst_dtype == QDV_F32 ? report_t<double, float>(view, pose, pose_cov, vel, bias) : report_t<double, double>(view, pose, pose_cov, vel, bias);
 }
@@ -138,6 +103,7 @@ static hipEvent_t g_ev[kMaxDevices][2] = {};
 static int order(const qle_device_view* v, hipStream_t first, hipStream_t then, int dir)
 {
     if (v->device < 0 || v->device >= kMaxDevices) return fail(QLE_ERR_INVALID, "device %d", v->device);
+    QLE_TRY(use_device(v));
     if (first == then) return QLE_OK;
     std::lock_guard<std::mutex> lock(g_ev_mu);
     hipEvent_t& ev = g_ev[v->device][dir];
@@ -149,12 +115,12 @@ static int order(const qle_device_view* v, hipStream_t first, hipStream_t then, 
 
 extern "C" int qdv_wait_stream(const qle_device_view* view, void* producer_stream)
 {
-    QDV_TRY(check_view(view));
+    QLE_TRY(check_view(view));
     return order(view, (hipStream_t)producer_stream, stream_of(view), 0);
 }
 
 extern "C" int qdv_signal_stream(const qle_device_view* view, void* consumer_stream)
 {
-    QDV_TRY(check_view(view));
+    QLE_TRY(check_view(view));
     return order(view, stream_of(view), (hipStream_t)consumer_stream, 1);
 }

@@ -4,79 +4,38 @@
 // the forecast goes into the caller's workspace (the host entry stages its host arrays through buffers of its own).
 #include "../../include/qle_lookahead.h"
 
-#include <hip/hip_runtime.h>
-
-#include <atomic>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <string>
-#include <type_traits>
 
 #include "ekf_lookahead.hpp"
 #include "ekf_params.hpp"
+#include "side_host.hpp"
 
 using namespace qle;
+using namespace qle::side;
 
 static_assert(QLK_MAX_HORIZON == kMaxHorizon, "the horizon cap of the header");
 
-static thread_local std::string g_err;
-static std::atomic<int64_t> g_launches{0};
+QLE_SIDE_LAST_ERROR(qlk_last_error)
+QLE_SIDE_LAUNCH_COUNT(qlk_launch_count)
 
-static int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-#define HIP_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(QLE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-#define QLK_TRY(expr)                  \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != QLE_OK) return rc_; \
-    } while (0)
-
-extern "C" const char* qlk_last_error(void) { return g_err.c_str(); }
-extern "C" int64_t qlk_launch_count(void) { return g_launches.load(std::memory_order_relaxed); }
-
-static bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-// what every entry refuses about the view; no GPU call
-static int check_view(const qle_device_view* v)
-{
-    if (!v) return fail(QLE_ERR_INVALID, "view is null");
-    if (v->struct_size != sizeof(qle_device_view)) return fail(QLE_ERR_INVALID, "view: struct_size %u, this library was built for %zu", v->struct_size, sizeof(qle_device_view));
-    if (v->dtype != QLE_F32 && v->dtype != QLE_F64) return fail(QLE_ERR_INVALID, "view: dtype %d", v->dtype);
-    if (v->batch <= 0 || v->padded_batch != padded_filters(v->batch)) return fail(QLE_ERR_INVALID, "view: batch %lld / padded %lld", (long long)v->batch, (long long)v->padded_batch);
-    if (!v->state || v->state_words != kSW) return fail(QLE_ERR_INVALID, "view: state records of %d words (this library: %d)", v->state_words, kSW);
-    if (!aligned(v->state, 16)) return fail(QLE_ERR_INVALID, "view: state must be 16-byte aligned");
-    if (v->num_states != 15 && v->num_states != 9) return fail(QLE_ERR_INVALID, "view: num_states %d", v->num_states);
-    if (v->compact && v->num_states != 9) return fail(QLE_ERR_INVALID, "view: compact records with num_states %d", v->num_states);
-    return QLE_OK;
-}
+// what every entry refuses about the view; no GPU call.  A view of exactly this library's size (the forecast is a copy of it), with
+// 16-byte aligned records.
+static int check_view(const qle_device_view* v) { return check_view(v, ViewSize::exact, true); }
 
 static int64_t workspace_bytes(const qle_device_view* v) { return v->padded_batch * (int64_t)kSW * (v->dtype == QLE_F64 ? 8 : 4); }
 
 extern "C" int64_t qlk_workspace_bytes(const qle_device_view* view)
 {
-    QLK_TRY(check_view(view));
+    QLE_TRY(check_view(view));
     return workspace_bytes(view);
 }
 
-// Everything that can be refused, in the order include/qle_lookahead.h lists it; no GPU call.  host: u, mask and ticks_to_limit are
-// host arrays (no alignment to ask for).
+// Everything include/qle_lookahead.h lists as refused, the view first; no GPU call.  host: u, mask and ticks_to_limit are host arrays
+// (no alignment to ask for).
 static int check_args(const qle_device_view* v, const qle_params* p, const void* u, int32_t u_dtype, int32_t h, const void* workspace,
                       int64_t ws_bytes, const qle_device_view* ahead, const qlk_coast* coast, const int32_t* ticks, bool host, CoastLimits* lim)
 {
-    QLK_TRY(check_view(v));
+    QLE_TRY(check_view(v));
     if (!p) return fail(QLE_ERR_INVALID, "params is null");
     if (v->num_states != (p->est_bias ? 15 : 9)) return fail(QLE_ERR_INVALID, "view: num_states %d, params: est_bias %d", v->num_states, p->est_bias);
     if (!u) return fail(QLE_ERR_INVALID, "u is null");
@@ -112,24 +71,19 @@ static int launch_t(const qle_device_view* v, const qle_params& pub, const qle_d
 {
     DevParams<T> dp = make_dev<T>(pub, der);
     dp.compact = v->compact ? 1 : 0;
-    const dim3 grid((unsigned)(v->padded_batch / kTile)), block(kTile);
-    hipStream_t s = (hipStream_t)v->stream;
     auto go = [&](auto pfp, auto compact) {
-        hipLaunchKernelGGL((k_lookahead<T, decltype(pfp)::value, decltype(compact)::value>), grid, block, 0, s, (const T*)v->state, (T*)c.workspace, c.u,
+        hipLaunchKernelGGL((k_lookahead<T, decltype(pfp)::value, decltype(compact)::value>), tiles(v), dim3(kTile), 0, stream_of(v), (const T*)v->state, (T*)c.workspace, c.u,
                            v->batch, c.h, c.u_f64, c.mask, (const T*)v->filter_params, c.ticks, c.lim, dp);
     };
-    auto with = [](bool b, auto&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); };
     with(v->filter_params != nullptr, [&](auto f) { with(v->compact != 0, [&](auto k) { go(f, k); }); });
-    HIP_TRY(hipGetLastError());
-    g_launches.fetch_add(1, std::memory_order_relaxed);   // counts launches the runtime took, not attempts
-    return QLE_OK;
+    return launched();
 }
 
 // the launch and the forecast view; the arguments are checked
 static int run(const qle_device_view* v, const qle_params* p, const qle_derived& der, const Call& c, qle_device_view* ahead)
 {
     const qle_device_view in = *v;   // ahead may be the struct the caller passed as view
-    QLK_TRY(in.dtype == QLE_F32 ? launch_t<float>(&in, *p, der, c) : launch_t<double>(&in, *p, der, c));
+    QLE_TRY(in.dtype == QLE_F32 ? launch_t<float>(&in, *p, der, c) : launch_t<double>(&in, *p, der, c));
     *ahead = in;
     ahead->state = c.workspace;
     return QLE_OK;
@@ -139,34 +93,24 @@ extern "C" int qlk_lookahead(const qle_device_view* view, const qle_params* para
                              void* workspace, int64_t ws_bytes, qle_device_view* ahead, const qlk_coast* coast, int32_t* ticks_to_limit)
 {
     CoastLimits lim;
-    QLK_TRY(check_args(view, params, u, u_dtype, h, workspace, ws_bytes, ahead, coast, ticks_to_limit, false, &lim));
+    QLE_TRY(check_args(view, params, u, u_dtype, h, workspace, ws_bytes, ahead, coast, ticks_to_limit, false, &lim));
     qle_derived der;
     if (qle_params_derive(params, &der) != QLE_OK) return fail(QLE_ERR_INVALID, "params: %s", qle_last_error());
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(view->device));
+    QLE_TRY(use_device(view));
     return run(view, params, der, Call{u, u_dtype == QLK_F64, h, mask, workspace, lim, ticks_to_limit}, ahead);
 }
-
-namespace {
-// device buffers of one qlk_lookahead_host call, freed however the call ends
-struct Staging {
-    void* p[3] = {nullptr, nullptr, nullptr};
-    ~Staging() { for (void* q : p) if (q) (void)hipFree(q); }
-};
-}  // namespace
 
 extern "C" int qlk_lookahead_host(const qle_device_view* view, const qle_params* params, const double* u, int32_t h, const uint8_t* mask,
                                   void* workspace, int64_t ws_bytes, qle_device_view* ahead, const qlk_coast* coast, int32_t* ticks_to_limit)
 {
     CoastLimits lim;
-    QLK_TRY(check_args(view, params, u, QLK_F64, h, workspace, ws_bytes, ahead, coast, ticks_to_limit, true, &lim));
+    QLE_TRY(check_args(view, params, u, QLK_F64, h, workspace, ws_bytes, ahead, coast, ticks_to_limit, true, &lim));
     qle_derived der;
     if (qle_params_derive(params, &der) != QLE_OK) return fail(QLE_ERR_INVALID, "params: %s", qle_last_error());
-    (void)hipGetLastError();
-    HIP_TRY(hipSetDevice(view->device));
+    QLE_TRY(use_device(view));
     hipStream_t s = (hipStream_t)view->stream;
     const size_t B = (size_t)view->batch;
-    Staging d;
+    Staging<3> d;
     HIP_TRY(hipMalloc(&d.p[0], B * kUW * sizeof(double)));
     HIP_TRY(hipMemcpyAsync(d.p[0], u, B * kUW * sizeof(double), hipMemcpyHostToDevice, s));
     if (mask) {
@@ -174,7 +118,7 @@ extern "C" int qlk_lookahead_host(const qle_device_view* view, const qle_params*
         HIP_TRY(hipMemcpyAsync(d.p[1], mask, B, hipMemcpyHostToDevice, s));
     }
     if (ticks_to_limit) HIP_TRY(hipMalloc(&d.p[2], B * sizeof(int32_t)));
-    QLK_TRY(run(view, params, der, Call{d.p[0], 1, h, (const uint8_t*)d.p[1], workspace, lim, (int32_t*)d.p[2]}, ahead));
+    QLE_TRY(run(view, params, der, Call{d.p[0], 1, h, (const uint8_t*)d.p[1], workspace, lim, (int32_t*)d.p[2]}, ahead));
     if (ticks_to_limit) HIP_TRY(hipMemcpyAsync(ticks_to_limit, d.p[2], B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return QLE_OK;

@@ -1,0 +1,138 @@
+// side_host.hpp -- the host scaffold the side libraries share (devio, gate, consistency, health, lookahead: csrc/Makefile, SIDE).
+// Host code only, every symbol internal: a library that includes it has an error string and a launch counter of its own, and
+// exports nothing it did not export before.  A *_capi.hip file keeps its static_asserts, the refusals that are its own, its launches
+// and its extern "C" entries; what every one of them needs around those is here.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <map>
+#include <mutex>
+#include <string>
+#include <type_traits>
+#include <utility>
+
+#include "../../include/qle_ekf.h"
+#include "ekf_layout.hpp"
+
+namespace qle {
+namespace side {
+namespace {
+
+thread_local std::string g_err;
+std::atomic<int64_t> g_launches{0};
+
+int fail(int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+#define HIP_TRY(expr)                                                                                  \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess) return fail(QLE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+#define QLE_TRY(expr)                  \
+    do {                               \
+        int rc_ = (expr);              \
+        if (rc_ != QLE_OK) return rc_; \
+    } while (0)
+// the two diagnostics entries of a library's header, over the library's own copies of the string and the counter
+#define QLE_SIDE_LAST_ERROR(name) extern "C" const char* name(void) { return qle::side::g_err.c_str(); }
+#define QLE_SIDE_LAUNCH_COUNT(name) extern "C" int64_t name(void) { return qle::side::g_launches.load(std::memory_order_relaxed); }
+
+// after every launch: counts the launches the runtime took, not attempts
+int launched()
+{
+    HIP_TRY(hipGetLastError());
+    g_launches.fetch_add(1, std::memory_order_relaxed);
+    return QLE_OK;
+}
+
+bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// view->struct_size: the libraries differ, on purpose, and say which rule they keep where they call check_view
+enum class ViewSize { exact, at_least };
+
+// What every entry refuses about the view; no GPU call.  state_aligned: also refuse records that are not 16-byte aligned.
+int check_view(const qle_device_view* v, ViewSize size, bool state_aligned)
+{
+    if (!v) return fail(QLE_ERR_INVALID, "view is null");
+    if (size == ViewSize::exact ? v->struct_size != sizeof(qle_device_view) : v->struct_size < sizeof(qle_device_view))
+        return fail(QLE_ERR_INVALID, "view: struct_size %u, this library was built for %zu", v->struct_size, sizeof(qle_device_view));
+    if (v->dtype != QLE_F32 && v->dtype != QLE_F64) return fail(QLE_ERR_INVALID, "view: dtype %d", v->dtype);
+    if (v->batch <= 0 || v->padded_batch != padded_filters(v->batch)) return fail(QLE_ERR_INVALID, "view: batch %lld / padded %lld", (long long)v->batch, (long long)v->padded_batch);
+    if (!v->state || v->state_words != kSW) return fail(QLE_ERR_INVALID, "view: state records of %d words (this library: %d)", v->state_words, kSW);
+    if (state_aligned && !aligned(v->state, 16)) return fail(QLE_ERR_INVALID, "view: state must be 16-byte aligned");
+    if (v->num_states != 15 && v->num_states != 9) return fail(QLE_ERR_INVALID, "view: num_states %d", v->num_states);
+    if (v->compact && v->num_states != 9) return fail(QLE_ERR_INVALID, "view: compact records with num_states %d", v->num_states);
+    return QLE_OK;
+}
+
+// the first GPU call of an entry, behind its refusals
+int use_device(const qle_device_view* v)
+{
+    (void)hipGetLastError();
+    HIP_TRY(hipSetDevice(v->device));
+    return QLE_OK;
+}
+
+inline dim3 tiles(const qle_device_view* v) { return dim3((unsigned)(v->padded_batch / kTile)); }
+inline hipStream_t stream_of(const qle_device_view* v) { return (hipStream_t)v->stream; }
+
+// a run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+void with(bool b, F&& f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// device buffers of one *_host call, freed however the call ends
+template <int N>
+struct Staging {
+    void* p[N] = {};
+    ~Staging() { for (void* q : p) if (q) (void)hipFree(q); }
+};
+
+// The [tiles][sums] partials of a batch summary: one buffer per (device, stream), grown on demand and kept -- two calls on one
+// stream are ordered, two streams never share a buffer.
+class Partials {
+public:
+    explicit Partials(int sums) : sums_(sums) {}
+    int get(const qle_device_view* v, int64_t tiles, double** out)
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        auto& slot = slots_[{v->device, v->stream}];
+        if (slot.second < tiles) {
+            if (slot.first) {
+                HIP_TRY(hipStreamSynchronize(stream_of(v)));   // a launch that reads the old buffer may be in flight
+                HIP_TRY(hipFree(slot.first));
+                slot = {nullptr, 0};
+            }
+            double* buf = nullptr;
+            HIP_TRY(hipMalloc(&buf, (size_t)tiles * sums_ * sizeof(double)));
+            slot = {buf, tiles};
+        }
+        *out = slot.first;
+        return QLE_OK;
+    }
+
+private:
+    const int sums_;
+    std::mutex mu_;
+    std::map<std::pair<int, void*>, std::pair<double*, int64_t>> slots_;
+};
+
+}  // namespace
+}  // namespace side
+}  // namespace qle

@@ -29,6 +29,7 @@ IMU sample held, computed in one read-only launch into a workspace of its own an
 Still host-fed through `BatchedRelativePoseEKF`: `set_state` and the per-filter stamps of `dynamic_meas_delay`
 (`filter_update(t_curr=..., apriltag_time=...)`).
 """
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -37,7 +38,7 @@ from . import consistency as _cons
 from . import gate as _gate
 from . import health as _health
 from . import lookahead as _look
-from ._lib import QLE_ERR_STATE, QLE_F32, QleDeviceView, QleInputsView, QleError, check, lib
+from ._lib import QLE_ERR_STATE, QLE_F32, QleDeviceView, QleInputsView, QleError, check, lib, load_side_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEVIO_LIB_PATH = os.environ.get("QLE_DEVIO_LIB") or os.path.join(_HERE, "libqle_devio.so")
@@ -62,15 +63,7 @@ def devio_lib():
     """Load libqle_devio.so; raises (never falls back) when it is missing."""
     global _dlib
     if _dlib is None:
-        if not os.path.exists(DEVIO_LIB_PATH):
-            raise ImportError(f"{DEVIO_LIB_PATH} not built: run `make -C quadrotor_landing_amd/csrc` (hipcc, gfx950). "
-                              "There is no fallback for the device-tensor boundary.")
-        L = C.CDLL(DEVIO_LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _dlib = L
+        _dlib = load_side_library(DEVIO_LIB_PATH, SYMBOLS, "the device-tensor boundary", needs_tick_library=False)
     return _dlib
 
 
@@ -136,6 +129,15 @@ class DeviceIO:
             return int(torch.cuda.current_stream(self.ekf.device).cuda_stream)
         return 0
 
+    @contextlib.contextmanager
+    def _ordered(self, D, view, *tensors):
+        """What the block queues on the handle's stream runs behind the caller's current stream, and that stream goes on behind it
+        (qdv_wait_stream ... qdv_signal_stream).  A call that raises in the block ends the bracket there: nothing is signalled."""
+        stream = self._current_stream(*tensors)
+        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
+        yield
+        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+
     def _view(self):
         v = QleDeviceView()
         v.struct_size = C.sizeof(QleDeviceView)
@@ -180,21 +182,19 @@ class DeviceIO:
         view = self._view()
         t = 0 if z is None else 1
         iv = self._inputs_view(t)
-        stream = self._current_stream(u, z, mask)
         out = None
         if chi2_max is not None:
             G = _gate.gate_lib()
             dn = self._out_dtype(None)
             accepted = self._alloc([(B,)], "uint8")[0]
             out = [accepted] + (self._alloc([(B,), (B, 6), (B, 6, 6)], dn) if return_nis else [None, None, None])
-        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
-        _dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), u.data_ptr(), None if z is None else z.data_ptr(),
-                                  None if mask is None else mask.data_ptr(), _FLOATS[src]))
-        if out is not None:
-            ptr = [None if o is None else o.data_ptr() for o in out]
-            _gate.gcheck(G.qgt_gate_tick(C.byref(view), C.byref(iv), C.byref(self.ekf.params), chi2_max, ptr[1], ptr[0], ptr[2], ptr[3],
-                                         _FLOATS[dn]))
-        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        with self._ordered(D, view, u, z, mask):
+            _dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), u.data_ptr(), None if z is None else z.data_ptr(),
+                                      None if mask is None else mask.data_ptr(), _FLOATS[src]))
+            if out is not None:
+                ptr = [None if o is None else o.data_ptr() for o in out]
+                _gate.gcheck(G.qgt_gate_tick(C.byref(view), C.byref(iv), C.byref(self.ekf.params), chi2_max, ptr[1], ptr[0], ptr[2], ptr[3],
+                                             _FLOATS[dn]))
         check(lib().qle_run(self.ekf._h, self._seq._h, t, 1))
         if out is not None:
             return tuple(out) if return_nis else out[0]
@@ -229,13 +229,11 @@ class DeviceIO:
         iv = self._inputs_view(1)
         zero_u = self._zeros_u(src)
         nu, S, nis = self._alloc([(B, 6), (B, 6, 6), (B,)], dn)
-        stream = self._current_stream(z, mask)
-        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
-        _dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), zero_u.data_ptr(), z.data_ptr(),
-                                  None if mask is None else mask.data_ptr(), _FLOATS[src]))
-        _gate.gcheck(G.qgt_innovation(C.byref(view), C.byref(iv), C.byref(self.ekf.params), nis.data_ptr(), nu.data_ptr(), S.data_ptr(),
-                                      _FLOATS[dn]))
-        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        with self._ordered(D, view, z, mask):
+            _dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), zero_u.data_ptr(), z.data_ptr(),
+                                      None if mask is None else mask.data_ptr(), _FLOATS[src]))
+            _gate.gcheck(G.qgt_innovation(C.byref(view), C.byref(iv), C.byref(self.ekf.params), nis.data_ptr(), nu.data_ptr(), S.data_ptr(),
+                                          _FLOATS[dn]))
         return nu, S, nis
 
     # ---- filter consistency against a truth
@@ -261,12 +259,10 @@ class DeviceIO:
         nees = self._alloc([(B,)], dn)[0]
         err = self._alloc([(B, n)], dn)[0] if return_err else None
         summary = self._alloc([(8,)], "float64")[0]
-        stream = self._current_stream(x_true, mask)
-        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
-        _cons.ccheck(K.qcs_nees(C.byref(view), C.byref(self.ekf.params), x_true.data_ptr(), _FLOATS[src],
-                                None if mask is None else mask.data_ptr(), bits, chi2_hi, nees.data_ptr(),
-                                None if err is None else err.data_ptr(), summary.data_ptr(), _FLOATS[dn]))
-        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        with self._ordered(D, view, x_true, mask):
+            _cons.ccheck(K.qcs_nees(C.byref(view), C.byref(self.ekf.params), x_true.data_ptr(), _FLOATS[src],
+                                    None if mask is None else mask.data_ptr(), bits, chi2_hi, nees.data_ptr(),
+                                    None if err is None else err.data_ptr(), summary.data_ptr(), _FLOATS[dn]))
         return (nees, err, summary) if return_err else (nees, summary)
 
     def _zeros_u(self, src):
@@ -289,10 +285,8 @@ class DeviceIO:
         view = self._view()
         iv = self._inputs_view(1)
         zero_u = self._zeros_u(src)
-        stream = self._current_stream(z, mask)
-        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
-        self._seed_from_slot(D, view, iv, zero_u, z, mask, src, reinit_bias)
-        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        with self._ordered(D, view, z, mask):
+            self._seed_from_slot(D, view, iv, zero_u, z, mask, src, reinit_bias)
 
     def _seed_from_slot(self, D, view, iv, zero_u, z, mask, src, reinit_bias):
         _dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), zero_u.data_ptr(), z.data_ptr(), None if mask is None else mask.data_ptr(),
@@ -317,11 +311,9 @@ class DeviceIO:
         view = self._view()
         status, flagged = self._alloc([(B,), (B,)], "uint8")
         summary = self._alloc([(len(_health.SUMMARY_FIELDS),)], "float64")[0] if return_summary else None
-        stream = self._current_stream(mask)
-        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
-        _health.hcheck(H.qhl_health(C.byref(view), C.byref(lim), None if mask is None else mask.data_ptr(), status.data_ptr(),
-                                    flagged.data_ptr(), None if summary is None else summary.data_ptr()))
-        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        with self._ordered(D, view, mask):
+            _health.hcheck(H.qhl_health(C.byref(view), C.byref(lim), None if mask is None else mask.data_ptr(), status.data_ptr(),
+                                        flagged.data_ptr(), None if summary is None else summary.data_ptr()))
         return (status, flagged, summary) if return_summary else (status, flagged)
 
     def retire(self, mask):
@@ -331,10 +323,8 @@ class DeviceIO:
         self._check_mask(mask, self.ekf.batch)
         D, H = devio_lib(), _health.health_lib()
         view = self._view()
-        stream = self._current_stream(mask)
-        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
-        _health.hcheck(H.qhl_retire(C.byref(view), mask.data_ptr()))
-        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        with self._ordered(D, view, mask):
+            _health.hcheck(H.qhl_retire(C.byref(view), mask.data_ptr()))
 
     def reseed(self, z, mask=None, reinit_bias=True, **limits):
         """Health check, then seed the flagged filters that have a detection: `health(**limits)` over every filter, reseeded =
@@ -358,13 +348,11 @@ class DeviceIO:
         iv = self._inputs_view(1)
         zero_u = self._zeros_u(src)
         status, reseeded = self._alloc([(B,), (B,)], "uint8")
-        stream = self._current_stream(z, mask)
-        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
-        _health.hcheck(H.qhl_health(C.byref(view), C.byref(lim), None, status.data_ptr(), reseeded.data_ptr(), None))
-        if mask is not None:
-            _health.hcheck(H.qhl_and_masks(C.byref(view), reseeded.data_ptr(), mask.data_ptr(), reseeded.data_ptr()))
-        self._seed_from_slot(D, view, iv, zero_u, z, reseeded, src, reinit_bias)
-        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        with self._ordered(D, view, z, mask):
+            _health.hcheck(H.qhl_health(C.byref(view), C.byref(lim), None, status.data_ptr(), reseeded.data_ptr(), None))
+            if mask is not None:
+                _health.hcheck(H.qhl_and_masks(C.byref(view), reseeded.data_ptr(), mask.data_ptr(), reseeded.data_ptr()))
+            self._seed_from_slot(D, view, iv, zero_u, z, reseeded, src, reinit_bias)
         return status, reseeded
 
     # ---- look-ahead: state and covariance h ticks ahead, read-only
@@ -389,12 +377,10 @@ class DeviceIO:
         workspace = self._alloc([(nbytes,)], "uint8")[0]
         ticks = self._alloc([(B,)], "int32")[0] if coast is not None else None
         ahead = QleDeviceView()
-        stream = self._current_stream(u, mask)
-        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
-        _look.kcheck(K.qlk_lookahead(C.byref(view), C.byref(self.ekf.params), u.data_ptr(), _FLOATS[src], h,
-                                     None if mask is None else mask.data_ptr(), workspace.data_ptr(), nbytes, C.byref(ahead),
-                                     None if coast is None else C.byref(coast), None if ticks is None else ticks.data_ptr()))
-        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        with self._ordered(D, view, u, mask):
+            _look.kcheck(K.qlk_lookahead(C.byref(view), C.byref(self.ekf.params), u.data_ptr(), _FLOATS[src], h,
+                                         None if mask is None else mask.data_ptr(), workspace.data_ptr(), nbytes, C.byref(ahead),
+                                         None if coast is None else C.byref(coast), None if ticks is None else ticks.data_ptr()))
         return _look.Forecast(self, ahead, workspace, h, ticks)
 
     def _check_mask(self, mask, B):
@@ -438,10 +424,8 @@ class DeviceIO:
                 raise ValueError("x, P and dtype must agree")
         D = devio_lib()
         view = self._view()
-        stream = self._current_stream(x, P)
-        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
-        _dcheck(D.qdv_unpack_state(C.byref(view), x.data_ptr(), P.data_ptr(), _FLOATS[dn]))
-        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        with self._ordered(D, view, x, P):
+            _dcheck(D.qdv_unpack_state(C.byref(view), x.data_ptr(), P.data_ptr(), _FLOATS[dn]))
         return x, P
 
     _REPORT = (("pose", (7,)), ("pose_cov", (6, 6)), ("vel", (3,)), ("bias", (6,)))
@@ -463,10 +447,8 @@ class DeviceIO:
         D = devio_lib()
         view = self._view()
         ptr = [out[k].data_ptr() if k in out else None for k, _ in self._REPORT]
-        stream = self._current_stream(*out.values())
-        _dcheck(D.qdv_wait_stream(C.byref(view), stream))
-        _dcheck(D.qdv_unpack_report(C.byref(view), ptr[0], ptr[1], ptr[2], ptr[3], _FLOATS[dn]))
-        _dcheck(D.qdv_signal_stream(C.byref(view), stream))
+        with self._ordered(D, view, *out.values()):
+            _dcheck(D.qdv_unpack_report(C.byref(view), ptr[0], ptr[1], ptr[2], ptr[3], _FLOATS[dn]))
         return out
 
     def close(self):

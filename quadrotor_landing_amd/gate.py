@@ -8,7 +8,7 @@ an error.
 import ctypes as C
 import os
 
-from ._lib import QleDeviceView, QleError, QleInputsView, QleParams, lib
+from ._lib import QleDeviceView, QleError, QleInputsView, QleParams, load_side_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 GATE_LIB_PATH = os.environ.get("QLE_GATE_LIB") or os.path.join(_HERE, "libqle_gate.so")
@@ -31,16 +31,7 @@ def gate_lib():
     """Load libqle_gate.so; raises (never falls back) when it is missing."""
     global _glib
     if _glib is None:
-        if not os.path.exists(GATE_LIB_PATH):
-            raise ImportError(f"{GATE_LIB_PATH} not built: run `make -C quadrotor_landing_amd/csrc` (hipcc, gfx950). "
-                              "There is no fallback for the gate in front of the fused tick.")
-        lib()   # libqle_gate.so takes qle_params_derive from the tick library: the same copy the handle uses
-        L = C.CDLL(GATE_LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _glib = L
+        _glib = load_side_library(GATE_LIB_PATH, SYMBOLS, "the gate in front of the fused tick", needs_tick_library=True)
     return _glib
 
 

@@ -10,7 +10,7 @@ error.
 import ctypes as C
 import os
 
-from ._lib import QleDeviceView, QleError
+from ._lib import QleDeviceView, QleError, load_side_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEALTH_LIB_PATH = os.environ.get("QLE_HEALTH_LIB") or os.path.join(_HERE, "libqle_health.so")
@@ -52,15 +52,7 @@ def health_lib():
     """Load libqle_health.so; raises (never falls back) when it is missing."""
     global _hlib
     if _hlib is None:
-        if not os.path.exists(HEALTH_LIB_PATH):
-            raise ImportError(f"{HEALTH_LIB_PATH} not built: run `make -C quadrotor_landing_amd/csrc` (hipcc, gfx950). "
-                              "There is no fallback for the lifecycle kernels.")
-        L = C.CDLL(HEALTH_LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _hlib = L
+        _hlib = load_side_library(HEALTH_LIB_PATH, SYMBOLS, "the lifecycle kernels", needs_tick_library=False)
     return _hlib
 
 

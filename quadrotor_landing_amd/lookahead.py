@@ -10,7 +10,7 @@ is an error.
 import ctypes as C
 import os
 
-from ._lib import QleDeviceView, QleError, QleParams
+from ._lib import QleDeviceView, QleError, QleParams, load_side_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LOOKAHEAD_LIB_PATH = os.environ.get("QLE_LOOKAHEAD_LIB") or os.path.join(_HERE, "libqle_lookahead.so")
@@ -43,15 +43,7 @@ def lookahead_lib():
     """Load libqle_lookahead.so; raises (never falls back) when it is missing."""
     global _klib
     if _klib is None:
-        if not os.path.exists(LOOKAHEAD_LIB_PATH):
-            raise ImportError(f"{LOOKAHEAD_LIB_PATH} not built: run `make -C quadrotor_landing_amd/csrc` (hipcc, gfx950). "
-                              "There is no fallback for the look-ahead kernel.")
-        L = C.CDLL(LOOKAHEAD_LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _klib = L
+        _klib = load_side_library(LOOKAHEAD_LIB_PATH, SYMBOLS, "the look-ahead kernel", needs_tick_library=True)
     return _klib
 
 
