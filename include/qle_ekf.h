@@ -230,6 +230,12 @@ int qle_get_measurement_delay(qle_batch *h, double *measurement_delay_curr);
 /* Measurement age used for dynamic_meas_delay when no per-filter stamps are given
  * (qle_step, qle_run): default = measurement_delay. */
 int qle_set_uniform_measurement_age(qle_batch *h, double seconds);
+/* Bookkeeping of the multirate history (read-only; tests and diagnostics): info = checkpoint spacing k, grid checkpoint
+ * slots Nc, IMU ring slots Cu, the tick counter, and the extra checkpoint's e_tick (tick whose state it holds, -1 none) and
+ * e_want (tick whose predict launch fills it next, -1 none) as the host holds them; hist_first [batch] (may be NULL) is
+ * the tick of each filter's oldest valid history entry, copied from the device after the handle's stream has drained.
+ * QLE_ERR_STATE for a handle without multirate_ekf. */
+int qle_get_history_info(qle_batch *h, int64_t info[6], int32_t *hist_first);
 /* After a tick: performed_correction (EKF.hpp:126), whether the pending measurement
  * was consumed (the reference clears measurement_ready, EKF.cpp:152) and
  * upds_since_correction (EKF.hpp:128).  Any pointer may be NULL. */

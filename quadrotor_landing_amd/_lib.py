@@ -124,6 +124,7 @@ SYMBOLS = {
     "qle_filter_update_stamped": (C.c_int, [_vp, _pd, _pd, _pu8, _d, _pd]),
     "qle_get_measurement_delay": (C.c_int, [_vp, _pd]),
     "qle_set_uniform_measurement_age": (C.c_int, [_vp, _d]),
+    "qle_get_history_info": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i32)]),
     "qle_get_tick_flags": (C.c_int, [_vp, _pu8, _pu8, C.POINTER(_i32)]),
     "qle_inputs_create": (C.c_int, [_vp, _i64, _pu8, C.POINTER(_vp)]),
     "qle_inputs_destroy": (C.c_int, [_vp]),

@@ -354,6 +354,11 @@ extern "C" int qle_create(qle_batch** out, int64_t batch, int32_t dtype, int32_t
         const long long v = std::atoll(s);
         if (v >= 16) h->rebase_at = v;
     }
+    // QLE_MR_K: the checkpoint spacing, one of the measured values (a policy knob for tests: mr_k is a kernel argument, not a template one)
+    if (const char* s = std::getenv("QLE_MR_K")) {
+        const int v = std::atoi(s);
+        if (v == 4 || v == 8 || v == 16 || v == 32 || v == 64) h->mr_k = v;
+    }
     // Workgroup size of the lane-per-filter kernels: 256 threads (4 tiles) at 65 536 and 131 072 filters; one wave per workgroup from
     // 262 144 filters on (finer dispatch: +2-3 % at 262 144 and 524 288 filters, +1.5 % at 1-2 M; profiles/r01_tuning.md section 4) and
     // BELOW 65 536 filters, where 256-thread workgroups leave CUs without work (32 768 filters are 128 of them on 256 CUs): predict tick
@@ -847,6 +852,21 @@ extern "C" int qle_set_uniform_measurement_age(qle_batch* h, double seconds)
 {
     QLE_TRY(check_handle(h));
     h->uniform_age = seconds;
+    return QLE_OK;
+}
+
+// The bookkeeping of the multirate history as the host holds it, and each filter's history start as the device does (read-only).
+extern "C" int qle_get_history_info(qle_batch* h, int64_t info[6], int32_t* hist_first)
+{
+    QLE_TRY(check_handle(h));
+    if (!info) return fail(QLE_ERR_INVALID, "info is null");
+    if (!h->mr || !h->hist_first) return fail(QLE_ERR_STATE, "the handle keeps no multirate history (multirate_ekf = 0)");
+    info[0] = h->mr_k; info[1] = h->mr_Nc; info[2] = h->mr_Cu;
+    info[3] = h->tick; info[4] = h->e_tick; info[5] = h->e_want;
+    if (hist_first) {
+        HIP_TRY(hipMemcpyAsync(hist_first, h->hist_first, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
     return QLE_OK;
 }
 

@@ -237,6 +237,15 @@ class BatchedRelativePoseEKF:
     def set_uniform_measurement_age(self, seconds):
         check(lib().qle_set_uniform_measurement_age(self._h, float(seconds)))
 
+    def history_info(self):
+        """Bookkeeping of the multirate history (read-only): dict of k, Nc, Cu, tick, e_tick, e_want as the host holds them and
+        hist_first [batch] int32 from the device (k_step_mr, ekf_multirate.hpp)."""
+        info = (C.c_int64 * 6)(); hf = np.zeros(self.batch, np.int32)
+        check(lib().qle_get_history_info(self._h, info, hf.ctypes.data_as(C.POINTER(C.c_int32))))
+        d = dict(zip(("k", "Nc", "Cu", "tick", "e_tick", "e_want"), (int(v) for v in info)))
+        d["hist_first"] = hf
+        return d
+
     def tick_flags(self):
         """(performed_correction, consumed, upds_since_correction) after the last tick."""
         pc = np.zeros(self.batch, np.uint8); co = np.zeros(self.batch, np.uint8); up = np.zeros(self.batch, np.int32)

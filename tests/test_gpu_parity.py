@@ -782,12 +782,13 @@ def test_multirate_replay_matches_reference_logic(cfg, dtype, T=60, loosen=1.0):
 
 
 def test_multirate_history_over_ring_wraps(dtype="f64"):
-    """The engine keeps the state in place, an IMU ring, a state checkpoint every 16 ticks and a per-filter anchor at the last
+    """The engine keeps the state in place, an IMU ring, a state checkpoint every 32 ticks and a per-filter anchor at the last
     correction, and rebuilds the entry a measurement belongs to by replaying from the newest checkpoint or the anchor (k_step_mr).
-    Measurements on ~45 % of the ticks with 0-300 ms of latency and no rate limit put corrections at every offset between
-    checkpoints, before and after the previous correction's entry; 260 ticks cross the 64-slot IMU ring four times and every
-    checkpoint slot several times.  Every tick must still match the reference logic (fp64: the randomly driven free run is too
-    long for an fp32-vs-fp64 comparison tick by tick)."""
+    Measurements on ~45 % of the ticks with 0-300 ms of latency and no rate limit spread the corrections' entries between the
+    checkpoints, before and after the previous correction's entry; with a 35-tick largest step delay the IMU ring has 128 slots
+    (4 checkpoint slots), and 260 ticks wrap it twice and reuse every checkpoint slot at least once.  Every tick must still match the
+    reference logic (fp64: the randomly driven free run is too long for an fp32-vs-fp64 comparison tick by tick; which start of
+    the chain a schedule reaches, and fp32 over ring wraps, are held by tests/test_gpu_multirate_history.py)."""
     test_multirate_replay_matches_reference_logic(
         dict(dynamic_meas_delay=1, measurement_delay=0.150, measurement_delay_max=0.350, dyn_measurement_delay_offset=0.085,
              limit_measurement_freq=0, **HW_TAGS), dtype, T=260, loosen=100.0)   # free run: rounding accumulates with the tick count
