@@ -92,20 +92,16 @@ extern "C" int qcs_nees_host(const qle_device_view* view, const qle_params* para
     QLE_TRY(use_device(view));
     hipStream_t s = (hipStream_t)view->stream;
     const size_t B = (size_t)view->batch, n = (size_t)view->num_states;
-    Staging<5> d;
-    HIP_TRY(hipMalloc(&d.p[0], B * 16 * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(d.p[0], x_true, B * 16 * sizeof(double), hipMemcpyHostToDevice, s));
-    if (mask) {
-        HIP_TRY(hipMalloc(&d.p[1], B));
-        HIP_TRY(hipMemcpyAsync(d.p[1], mask, B, hipMemcpyHostToDevice, s));
-    }
-    if (nees) HIP_TRY(hipMalloc(&d.p[2], B * sizeof(double)));
-    if (err) HIP_TRY(hipMalloc(&d.p[3], B * n * sizeof(double)));
-    if (summary) HIP_TRY(hipMalloc(&d.p[4], sizeof(qcs_summary)));
-    QLE_TRY(run(view, params, Call{d.p[0], 1, (const uint8_t*)d.p[1], blocks, chi2_hi, d.p[2], d.p[3], (double*)d.p[4], 1}));
-    if (nees) HIP_TRY(hipMemcpyAsync(nees, d.p[2], B * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (err) HIP_TRY(hipMemcpyAsync(err, d.p[3], B * n * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (summary) HIP_TRY(hipMemcpyAsync(summary, d.p[4], sizeof(qcs_summary), hipMemcpyDeviceToHost, s));
+    DeviceMem own;
+    void* d[5] = {};
+    HIP_TRY(own.acquire({{d[0], B * 16 * sizeof(double)}, {d[1], mask ? B : 0}, {d[2], nees ? B * sizeof(double) : 0}, {d[3], err ? B * n * sizeof(double) : 0},
+                         {d[4], summary ? sizeof(qcs_summary) : 0}}));
+    HIP_TRY(hipMemcpyAsync(d[0], x_true, B * 16 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (mask) HIP_TRY(hipMemcpyAsync(d[1], mask, B, hipMemcpyHostToDevice, s));
+    QLE_TRY(run(view, params, Call{d[0], 1, (const uint8_t*)d[1], blocks, chi2_hi, d[2], d[3], (double*)d[4], 1}));
+    if (nees) HIP_TRY(hipMemcpyAsync(nees, d[2], B * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (err) HIP_TRY(hipMemcpyAsync(err, d[3], B * n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (summary) HIP_TRY(hipMemcpyAsync(summary, d[4], sizeof(qcs_summary), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return QLE_OK;
 }

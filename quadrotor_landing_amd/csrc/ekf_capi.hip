@@ -192,7 +192,7 @@ extern "C" int qle_set_params(qle_batch* h, const qle_params* p)
     QLE_TRY(qle_params_derive(p, &d));
     // The state is one record array, updated in place.  The multirate EKF (EKF.cpp:196-236) keeps its history next to it: an IMU
     // ring, a state checkpoint every mr_k ticks and one anchor slot (k_step_mr, ekf_multirate.hpp), sized for the largest step delay
-    // the parameters allow (EKF.cpp:199-201).  Everything is allocated into locals; the handle changes only when all of it exists.
+    // the parameters allow (EKF.cpp:199-201).  The handle changes only when all of it exists (DeviceMem::acquire): until then the old history serves.
     const bool mr = p->multirate_ekf != 0;
     int32_t Nc = 0, Cu = 0;
     if (mr) {
@@ -201,41 +201,16 @@ extern "C" int qle_set_params(qle_batch* h, const qle_params* p)
         Nc = (step_max + h->mr_k + 1 + h->mr_k - 1) / h->mr_k + 1;
         Cu = Nc * h->mr_k;
     }
-    if (!h->ring) {
-        void* nr = nullptr;
-        hipError_t e = hipMalloc(&nr, slot_bytes(h));
+    if (!h->ring) {   // all-zero records = filters not initialised
+        hipError_t e = h->mem.acquire({{h->ring, slot_bytes(h), true}}, h->stream);
         if (e != hipSuccess) return fail(QLE_ERR_NOMEM, "hipMalloc of the state (%lld filters): %s", (long long)h->Bp, hipGetErrorString(e));
-        e = hipMemsetAsync(nr, 0, slot_bytes(h), h->stream);   // all-zero records = filters not initialised
-        if (e != hipSuccess) { (void)hipFree(nr); return fail(QLE_ERR_HIP, "state setup: %s", hipGetErrorString(e)); }
-        h->ring = nr;
     }
     if (mr && (!h->hist_first || Nc != h->mr_Nc)) {
-        int32_t* hf = nullptr;
-        double *stp = nullptr, *dc = nullptr;
-        void *mu = nullptr, *mc = nullptr, *ma = nullptr;
-        const size_t ub = (size_t)Cu * kHW * (size_t)h->Bp * h->wsz, cb = (size_t)(Nc + 1) * slot_bytes(h);   // Nc grid checkpoints + the extra one
-        hipError_t e = hipMalloc((void**)&hf, sizeof(int32_t) * (size_t)h->Bp);
-        if (e == hipSuccess) e = hipMalloc((void**)&stp, sizeof(double) * (size_t)h->Bp);
-        if (e == hipSuccess) e = hipMalloc((void**)&dc, sizeof(double) * (size_t)h->Bp);
-        if (e == hipSuccess) e = hipMalloc(&mu, ub);
-        if (e == hipSuccess) e = hipMalloc(&mc, cb);
-        if (e == hipSuccess) e = hipMalloc(&ma, slot_bytes(h));
-        if (e == hipSuccess) e = hipMemsetAsync(dc, 0, sizeof(double) * (size_t)h->Bp, h->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(stp, 0, sizeof(double) * (size_t)h->Bp, h->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(mu, 0, ub, h->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(mc, 0, cb, h->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(ma, 0, slot_bytes(h), h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) {
-            void* tmp[] = {hf, stp, dc, mu, mc, ma};
-            for (void* b : tmp)
-                if (b) (void)hipFree(b);
+        const size_t per = sizeof(double) * (size_t)h->Bp, ub = (size_t)Cu * kHW * (size_t)h->Bp * h->wsz, cb = (size_t)(Nc + 1) * slot_bytes(h);   // Nc grid checkpoints + the extra one
+        hipError_t e = h->mem.acquire({{h->hist_first, sizeof(int32_t) * (size_t)h->Bp}, {h->stamp, per, true}, {h->delay_cur, per, true}, {h->mr_u, ub, true},
+                                       {h->mr_ckpt, cb, true}, {h->mr_anchor, slot_bytes(h), true}}, h->stream, true);
+        if (e != hipSuccess)
             return fail(QLE_ERR_NOMEM, "multirate history (%d checkpoint slots, %d IMU slots x %lld filters): %s", Nc, Cu, (long long)h->Bp, hipGetErrorString(e));
-        }
-        void* old[] = {h->hist_first, h->stamp, h->delay_cur, h->mr_u, h->mr_ckpt, h->mr_anchor};
-        for (void* b : old)
-            if (b) (void)hipFree(b);
-        h->hist_first = hf; h->stamp = stp; h->delay_cur = dc; h->mr_u = mu; h->mr_ckpt = mc; h->mr_anchor = ma;
         h->mr_Nc = Nc; h->mr_Cu = Cu;
     }
     // Record layout (ekf_layout.hpp): est_bias = false without the multirate history keeps only the 9 x 9 pose block of P (compact
@@ -266,10 +241,7 @@ extern "C" int qle_destroy(qle_batch* h)
     if (!h) return QLE_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->ring, h->pfp, h->aux_accel, h->aux_obs, h->tick_u, h->tick_z, h->stage, h->stage_mask, h->counter, h->last_corr, h->flags, h->hist_first, h->stamp,
-                    h->delay_cur, h->mr_u, h->mr_ckpt, h->mr_anchor, h->innov, h->innov_nis};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
+    h->mem.release_all();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -376,19 +348,11 @@ extern "C" int qle_create(qle_batch** out, int64_t batch, int32_t dtype, int32_t
     if (hipSetDevice(device) != hipSuccess) return bail(fail(QLE_ERR_HIP, "hipSetDevice(%d) failed", device));
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(QLE_ERR_HIP, "hipStreamCreate failed"));
     if ((rc = qle_set_params(h, p)) != QLE_OK) return bail(rc);
-#define ALLOC(ptr, bytes)                                                                               \
-    do {                                                                                                \
-        hipError_t ea_ = hipMalloc((void**)&(ptr), (bytes));                                            \
-        if (ea_ != hipSuccess) return bail(fail(QLE_ERR_NOMEM, "hipMalloc(%zu B) for %s: %s", (size_t)(bytes), #ptr, hipGetErrorString(ea_))); \
-    } while (0)
     if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) return bail(fail(QLE_ERR_HIP, "hipEventCreate failed"));
     const size_t B = (size_t)h->Bp, w = h->wsz;
-    ALLOC(h->tick_u, kUW * B * w);
-    ALLOC(h->tick_z, kZW * B * w);
-    ALLOC(h->stage, (size_t)kStageDoubles * sizeof(double));
-    ALLOC(h->stage_mask, (size_t)kStageFilters);
-    ALLOC(h->counter, sizeof(unsigned long long));
-#undef ALLOC
+    e = h->mem.acquire({{h->tick_u, kUW * B * w}, {h->tick_z, kZW * B * w}, {h->stage, (size_t)kStageDoubles * sizeof(double)}, {h->stage_mask, (size_t)kStageFilters},
+                        {h->counter, sizeof(unsigned long long)}});
+    if (e != hipSuccess) return bail(fail(QLE_ERR_NOMEM, "hipMalloc of the tick inputs and staging buffers (%lld filters): %s", (long long)h->Bp, hipGetErrorString(e)));
     *out = h;
     return QLE_OK;
 }
@@ -400,7 +364,7 @@ extern "C" int32_t qle_num_states(const qle_batch* h) { return h ? h->der.num_st
 extern "C" int64_t qle_algorithmic_bytes(const qle_batch* h, int32_t kind)
 {   // packed P, SoA, one streamed tick
     if (!h) return 0;
-    const int64_t rec = h->compact ? 16 + kPWc : 136;   // state words a tick reads and writes (compact records: x + the 9 x 9 pose block of P)
+    const int64_t rec = record_words(h);   // state words a tick reads and writes (compact records: x + the 9 x 9 pose block of P)
     int64_t words = kind == 0 ? (rec + 6) + rec : kind == 1 ? (rec + 6 + 7) + rec : (rec + 7) + rec;
     if (h->pfp_on) words += kFW;
     int64_t bytes = words * (int64_t)h->wsz * h->B;
@@ -420,7 +384,7 @@ extern "C" int qle_get_policy(const qle_batch* h, qle_policy* out)
     out->block = h->block;
     out->coop_ticks = h->mr ? 0 : h->quad;
     out->ring_slots = h->mr ? h->mr_Nc + 1 : 1;
-    out->record_words = h->compact ? kXW + kPWc : kXW + kPW;
+    out->record_words = record_words(h);
     out->reserved = 0;
     out->state_bytes = (int64_t)slot_bytes(h);
     // what a tick touches again later: the state itself, plus (multirate) the history it streams to
@@ -451,79 +415,95 @@ extern "C" int qle_timer_end(qle_batch* h, float* ms)
 }
 
 // --------------------------------------------------- staging (not hot path)
-// Chunked AoS fp64 host -> device tiles.  `W` words per filter taken from a
-// host row of `stride` doubles go to words [w0, w0+W) of the WT-word record.
-template <typename T>
-static int pack_rows(qle_batch* h, const double* host, int stride, int W, void* dst, int WT, int w0)
+// AoS fp64 host arrays <-> device records, through the handle's staging buffer in chunks of at most `chunk` filters.  copy(i0, n) enqueues
+// the copies between host and buffer for filters [i0, i0 + n), kernel(i0, n) the launch that packs or unpacks them: the copies first on the
+// way to the device, the kernel first on the way back.  The stream is waited for before the next chunk reuses the buffer.
+template <typename Copy, typename Kernel>
+static int for_chunks(qle_batch* h, int64_t chunk, bool to_dev, Copy&& copy, Kernel&& kernel)
 {
-    const int64_t chunk = std::min<int64_t>(kStageFilters, kStageDoubles / std::max(stride, 1));
     for (int64_t i0 = 0; i0 < h->B; i0 += chunk) {
         const int64_t n = std::min(chunk, h->B - i0);
-        HIP_TRY(hipMemcpyAsync(h->stage, host + i0 * stride, (size_t)n * stride * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        QLE_TRY(launch(h, k_pack_off<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const double*)h->stage, stride, W, (T*)dst, WT, w0, i0, n));
-        HIP_TRY(hipStreamSynchronize(h->stream));  // staging buffer is reused by the next chunk
-    }
-    return QLE_OK;
-}
-template <typename T>
-static int unpack_rows(qle_batch* h, const void* src, int stride, int W, double* host, int WT, int w0)
-{
-    const int64_t chunk = std::min<int64_t>(kStageFilters, kStageDoubles / std::max(stride, 1));
-    for (int64_t i0 = 0; i0 < h->B; i0 += chunk) {
-        const int64_t n = std::min(chunk, h->B - i0);
-        QLE_TRY(launch(h, k_unpack_off<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const T*)src, stride, W, h->stage, WT, w0, i0, n));
-        HIP_TRY(hipMemcpyAsync(host + i0 * stride, h->stage, (size_t)n * stride * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (to_dev) QLE_TRY(copy(i0, n));
+        QLE_TRY(kernel(i0, n));
+        if (!to_dev) QLE_TRY(copy(i0, n));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return QLE_OK;
 }
-template <typename T>
-static int pack_z(qle_batch* h, const double* z, const uint8_t* mask, void* dst)
+static inline dim3 grid256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+// The direction of a staged call is the constness of its host array: a const one is the source, any other one the destination.
+template <typename H> constexpr bool to_device = std::is_const<H>::value;
+template <typename H>
+static int stage_copy(qle_batch* h, H* host, int64_t first, void* staged, size_t bytes)   // host: null = not asked for
 {
-    for (int64_t i0 = 0; i0 < h->B; i0 += kStageFilters) {
-        const int64_t n = std::min(kStageFilters, h->B - i0);
-        if (z) HIP_TRY(hipMemcpyAsync(h->stage, z + i0 * 7, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        if (mask) HIP_TRY(hipMemcpyAsync(h->stage_mask, mask + i0, (size_t)n, hipMemcpyHostToDevice, h->stream));
-        QLE_TRY(launch(h, k_pack_z_off<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, z ? (const double*)h->stage : nullptr,
-                       mask ? (const uint8_t*)h->stage_mask : nullptr, (T*)dst, i0, n));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
+    if (!host) return QLE_OK;
+    if constexpr (to_device<H>) HIP_TRY(hipMemcpyAsync(staged, host + first, bytes, hipMemcpyHostToDevice, h->stream));
+    else HIP_TRY(hipMemcpyAsync(host + first, staged, bytes, hipMemcpyDeviceToHost, h->stream));
     return QLE_OK;
 }
-template <typename T>
-static int pack_P(qle_batch* h, const double* P, void* dst)
+// `W` words per filter of a host row of `stride` doubles <-> words [w0, w0+W) of the WT-word record.
+template <typename T, typename H>
+static int stage_rows(qle_batch* h, H* host, int stride, int W, void* rec, int WT, int w0)
+{
+    return for_chunks(
+        h, std::min<int64_t>(kStageFilters, kStageDoubles / std::max(stride, 1)), to_device<H>,
+        [&](int64_t i0, int64_t n) { return stage_copy(h, host, i0 * stride, h->stage, (size_t)n * stride * sizeof(double)); },
+        [&](int64_t i0, int64_t n) {
+            if constexpr (to_device<H>) return launch(h, k_pack_off<T>, grid256(n), dim3(256), 0, (const double*)h->stage, stride, W, (T*)rec, WT, w0, i0, n);
+            else return launch(h, k_unpack_off<T>, grid256(n), dim3(256), 0, (const T*)rec, stride, W, h->stage, WT, w0, i0, n);
+        });
+}
+// tag poses z [B][7] and their mask bytes <-> a record of tag poses
+template <typename T, typename H, typename M>
+static int stage_z(qle_batch* h, H* z, M* mask, void* rec)
+{
+    static_assert(to_device<H> == to_device<M>, "z and mask go the same way");
+    return for_chunks(
+        h, kStageFilters, to_device<H>,
+        [&](int64_t i0, int64_t n) -> int {
+            QLE_TRY(stage_copy(h, z, i0 * 7, h->stage, (size_t)n * 7 * sizeof(double)));
+            return stage_copy(h, mask, i0, h->stage_mask, (size_t)n);
+        },
+        [&](int64_t i0, int64_t n) {
+            if constexpr (to_device<H>)
+                return launch(h, k_pack_z_off<T>, grid256(n), dim3(256), 0, z ? (const double*)h->stage : nullptr, mask ? (const uint8_t*)h->stage_mask : nullptr,
+                              (T*)rec, i0, n);
+            else return launch(h, k_unpack_z_off<T>, grid256(n), dim3(256), 0, (const T*)rec, h->stage, h->stage_mask, i0, n);
+        });
+}
+// P [B][n][n] <-> the packed covariance words of the state records
+template <typename T, typename H>
+static int stage_P(qle_batch* h, H* P, void* rec)
 {
     const int n = h->der.num_states;
-    for (int64_t i0 = 0; i0 < h->B; i0 += kStageFilters) {
-        const int64_t m = std::min(kStageFilters, h->B - i0);
-        HIP_TRY(hipMemcpyAsync(h->stage, P + i0 * n * n, (size_t)m * n * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        QLE_TRY(launch(h, k_pack_P_off<T>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (const double*)h->stage, n, (T*)dst, i0, m, (int)h->compact));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return QLE_OK;
-}
-template <typename T>
-static int unpack_P(qle_batch* h, const void* src, double* P)
-{
-    const int n = h->der.num_states;
-    for (int64_t i0 = 0; i0 < h->B; i0 += kStageFilters) {
-        const int64_t m = std::min(kStageFilters, h->B - i0);
-        QLE_TRY(launch(h, k_unpack_P_off<T>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (const T*)src, n, h->stage, i0, m, (int)h->compact));
-        HIP_TRY(hipMemcpyAsync(P + i0 * n * n, h->stage, (size_t)m * n * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return QLE_OK;
+    return for_chunks(
+        h, kStageFilters, to_device<H>, [&](int64_t i0, int64_t m) { return stage_copy(h, P, i0 * n * n, h->stage, (size_t)m * n * n * sizeof(double)); },
+        [&](int64_t i0, int64_t m) {
+            if constexpr (to_device<H>) return launch(h, k_pack_P_off<T>, grid256(m), dim3(256), 0, (const double*)h->stage, n, (T*)rec, i0, m, (int)h->compact);
+            else return launch(h, k_unpack_P_off<T>, grid256(m), dim3(256), 0, (const T*)rec, n, h->stage, i0, m, (int)h->compact);
+        });
 }
 
+// index of the tick before the next one, for every filter: "as if tick - 1 had corrected" (upds_since_correction = 0, EKF.cpp:77) or "the
+// history starts at tick - 1"
+template <typename I>
+static int seed_prev_tick(qle_batch* h, I* ticks) { return launch(h, k_fill_i32<I>, grid_for(h, 256), dim3(256), 0, ticks, (I)(h->tick - 1), h->B); }
+// per-filter parameters are allocated by whichever call first provides them (qle_set_filter_params, the generator)
+static int need_pfp(qle_batch* h)
+{
+    if (h->pfp) return QLE_OK;
+    hipError_t e = h->mem.acquire({{h->pfp, kFW * (size_t)h->Bp * h->wsz}});
+    return e == hipSuccess ? QLE_OK : fail(QLE_ERR_HIP, "hipMalloc of the per-filter parameters (%lld filters): %s", (long long)h->Bp, hipGetErrorString(e));
+}
 
 extern "C" int qle_set_state(qle_batch* h, const double* x, const double* P)
 {
     QLE_TRY(check_handle(h));
     if (!x || !P) return fail(QLE_ERR_INVALID, "x and P must be non-null");
-    QLE_TRY(BY_DTYPE(h, pack_rows, h, x, kXW, kXW, state_cur(h), kSW, 0));
-    QLE_TRY(BY_DTYPE(h, pack_P, h, P, state_cur(h)));
+    QLE_TRY(BY_DTYPE(h, stage_rows, h, x, kXW, kXW, state_cur(h), kSW, 0));
+    QLE_TRY(BY_DTYPE(h, stage_P, h, P, state_cur(h)));
     if (!h->state_set && h->last_corr) {   // first state of the handle: upds_since_correction = 0 now (EKF.cpp:77)
-        QLE_TRY(launch(h, k_fill_i32<int32_t>, grid_for(h, 256), dim3(256), 0, h->last_corr, (int32_t)(h->tick - 1), h->B));
+        QLE_TRY(seed_prev_tick(h, h->last_corr));
     }
     h->state_set = true;
     h->hist_dirty = true;
@@ -532,8 +512,8 @@ extern "C" int qle_set_state(qle_batch* h, const double* x, const double* P)
 extern "C" int qle_get_state(qle_batch* h, double* x, double* P)
 {
     QLE_TRY(check_handle(h));
-    if (x) QLE_TRY(BY_DTYPE(h, unpack_rows, h, state_cur(h), kXW, kXW, x, kSW, 0));
-    if (P) QLE_TRY(BY_DTYPE(h, unpack_P, h, state_cur(h), P));
+    if (x) QLE_TRY(BY_DTYPE(h, stage_rows, h, x, kXW, kXW, state_cur(h), kSW, 0));
+    if (P) QLE_TRY(BY_DTYPE(h, stage_P, h, P, state_cur(h)));
     return QLE_OK;
 }
 
@@ -541,8 +521,8 @@ extern "C" int qle_set_filter_params(qle_batch* h, const double* pfp)
 {
     QLE_TRY(check_handle(h));
     if (!pfp) { h->pfp_on = false; return QLE_OK; }
-    if (!h->pfp) HIP_TRY(hipMalloc(&h->pfp, kFW * (size_t)h->Bp * h->wsz));
-    QLE_TRY(BY_DTYPE(h, pack_rows, h, pfp, kFW, kFW, h->pfp, kFW, 0));
+    QLE_TRY(need_pfp(h));
+    QLE_TRY(BY_DTYPE(h, stage_rows, h, pfp, kFW, kFW, h->pfp, kFW, 0));
     h->pfp_on = true;
     return QLE_OK;
 }
@@ -552,24 +532,16 @@ extern "C" int qle_get_filter_params(qle_batch* h, double* pfp)
     QLE_TRY(check_handle(h));
     if (!pfp) return fail(QLE_ERR_INVALID, "pfp is null");
     if (!h->pfp || !h->pfp_on) return fail(QLE_ERR_STATE, "no per-filter parameters are set (qle_set_filter_params, or qle_synth_generate with perturb_filter_params)");
-    return BY_DTYPE(h, unpack_rows, h, h->pfp, kFW, kFW, pfp, kFW, 0);
+    return BY_DTYPE(h, stage_rows, h, pfp, kFW, kFW, h->pfp, kFW, 0);
 }
 
 extern "C" int qle_enable_aux(qle_batch* h, int32_t on)
 {
     QLE_TRY(check_handle(h));
     if (on && !h->aux_accel) {
-        void *a = nullptr, *o = nullptr;
-        hipError_t e = hipMalloc(&a, 3 * (size_t)h->B * h->wsz);
-        if (e == hipSuccess) e = hipMalloc(&o, 7 * (size_t)h->B * h->wsz);
-        if (e == hipSuccess) e = hipMemsetAsync(a, 0, 3 * (size_t)h->B * h->wsz, h->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(o, 0, 7 * (size_t)h->B * h->wsz, h->stream);
-        if (e != hipSuccess) {
-            if (a) (void)hipFree(a);
-            if (o) (void)hipFree(o);
-            return fail(QLE_ERR_NOMEM, "side-output buffers: %s", hipGetErrorString(e));
-        }
-        h->aux_accel = a; h->aux_obs = o;
+        const size_t per = (size_t)h->B * h->wsz;
+        hipError_t e = h->mem.acquire({{h->aux_accel, 3 * per, true}, {h->aux_obs, 7 * per, true}}, h->stream);
+        if (e != hipSuccess) return fail(QLE_ERR_NOMEM, "side-output buffers: %s", hipGetErrorString(e));
     }
     h->aux = on != 0;
     return QLE_OK;
@@ -603,7 +575,7 @@ extern "C" int qle_get_aux(qle_batch* h, double* accel_rel, double* obs)
 int mr_prepare(qle_batch* h)
 {
     if (h->mr && h->hist_dirty) {   // every filter's history = the single entry "state now": anchor <- state, hist_first = tick-1
-        QLE_TRY(launch(h, k_fill_i32<int32_t>, grid_for(h, 256), dim3(256), 0, h->hist_first, (int32_t)(h->tick - 1), h->B));
+        QLE_TRY(seed_prev_tick(h, h->hist_first));
         HIP_TRY(hipMemcpyAsync(h->mr_anchor, state_cur(h), slot_bytes(h), hipMemcpyDeviceToDevice, h->stream));
         h->e_tick = h->e_want = h->last_mr_launch = -1;
     }
@@ -664,9 +636,9 @@ extern "C" int qle_predict(qle_batch* h, const double* u)
     QLE_TRY(check_handle(h));
     QLE_TRY(need_state(h));
     if (!u) return fail(QLE_ERR_INVALID, "u is null");
-    QLE_TRY(BY_DTYPE(h, pack_rows, h, u, kUW, kUW, h->tick_u, kUW, 0));
+    QLE_TRY(BY_DTYPE(h, stage_rows, h, u, kUW, kUW, h->tick_u, kUW, 0));
     h->hist_dirty = true;  // a bare prediction_step is not a filter tick: the multirate history restarts
-    if ((h->quad & 2) && !h->compact) return BY_DTYPE(h, launch_quad, h, h->tick_u, nullptr);
+    if (use_quad_bare(h, 2)) return BY_DTYPE(h, launch_quad, h, h->tick_u, nullptr);
     return BY_DTYPE(h, launch_predict_sd, h, h->tick_u, state_cur(h), state_cur(h), false);
 }
 extern "C" int qle_update(qle_batch* h, const double* z, const uint8_t* mask)
@@ -674,7 +646,7 @@ extern "C" int qle_update(qle_batch* h, const double* z, const uint8_t* mask)
     QLE_TRY(check_handle(h));
     QLE_TRY(need_state(h));
     if (!z) return fail(QLE_ERR_INVALID, "z is null");
-    QLE_TRY(BY_DTYPE(h, pack_z, h, z, mask, h->tick_z));
+    QLE_TRY(BY_DTYPE(h, stage_z, h, z, mask, h->tick_z));
     h->hist_dirty = true;
     return BY_DTYPE(h, launch_update, h, h->tick_z);
 }
@@ -683,11 +655,11 @@ extern "C" int qle_step(qle_batch* h, const double* u, const double* z, const ui
     QLE_TRY(check_handle(h));
     QLE_TRY(need_state(h));
     if (!u) return fail(QLE_ERR_INVALID, "u is null");
-    QLE_TRY(BY_DTYPE(h, pack_rows, h, u, kUW, kUW, h->tick_u, kUW, 0));
+    QLE_TRY(BY_DTYPE(h, stage_rows, h, u, kUW, kUW, h->tick_u, kUW, 0));
     if (!z) {
         QLE_TRY(BY_DTYPE(h, launch_predict, h, h->tick_u));
     } else {
-        QLE_TRY(BY_DTYPE(h, pack_z, h, z, mask, h->tick_z));
+        QLE_TRY(BY_DTYPE(h, stage_z, h, z, mask, h->tick_z));
         QLE_TRY(BY_DTYPE(h, launch_step, h, h->tick_u, h->tick_z));
     }
     return advance_tick(h);
@@ -698,33 +670,25 @@ extern "C" int qle_step(qle_batch* h, const double* u, const double* z, const ui
 static int innov_alloc(qle_batch* h)
 {
     if (h->innov) return QLE_OK;
-    void *d = nullptr, *n = nullptr;
-    hipError_t e = hipMalloc(&d, (size_t)kDW * (size_t)h->Bp * h->wsz);
-    if (e == hipSuccess) e = hipMalloc(&n, (size_t)h->Bp * h->wsz);
-    if (e != hipSuccess) {
-        if (d) (void)hipFree(d);
-        if (n) (void)hipFree(n);
-        return fail(QLE_ERR_NOMEM, "innovation outputs: %s", hipGetErrorString(e));
-    }
-    h->innov = d; h->innov_nis = n;
-    return QLE_OK;
+    hipError_t e = h->mem.acquire({{h->innov, (size_t)kDW * (size_t)h->Bp * h->wsz}, {h->innov_nis, (size_t)h->Bp * h->wsz}});
+    return e == hipSuccess ? QLE_OK : fail(QLE_ERR_NOMEM, "innovation outputs: %s", hipGetErrorString(e));
 }
 // Host copies of the last k_innov launch's outputs (chunked staging; synchronises).  accepted = the mask words of h->tick_z.
 template <typename T>
 static int innov_read_t(qle_batch* h, double* nu, double* S, double* nis, uint8_t* accepted)
 {
-    if (nu) QLE_TRY(unpack_rows<T>(h, h->innov, 6, 6, nu, kDW, 0));
+    if (nu) QLE_TRY(stage_rows<T>(h, nu, 6, 6, h->innov, kDW, 0));
     if (S) {
         std::vector<double> sp((size_t)h->B * 21);
-        QLE_TRY(unpack_rows<T>(h, h->innov, 21, 21, sp.data(), kDW, 6));
+        QLE_TRY(stage_rows<T>(h, sp.data(), 21, 21, h->innov, kDW, 6));
         for (int64_t i = 0; i < h->B; ++i)
             for (int a = 0; a < 6; ++a)
                 for (int b = 0; b < 6; ++b) S[i * 36 + a * 6 + b] = sp[(size_t)i * 21 + (a <= b ? sidx6(a, b) : sidx6(b, a))];
     }
-    if (nis) QLE_TRY(unpack_rows<T>(h, h->innov_nis, 1, 1, nis, 1, 0));
+    if (nis) QLE_TRY(stage_rows<T>(h, nis, 1, 1, h->innov_nis, 1, 0));
     if (accepted) {
         std::vector<double> m((size_t)h->B);
-        QLE_TRY(unpack_rows<T>(h, h->tick_z, 1, 1, m.data(), kZW, 7));
+        QLE_TRY(stage_rows<T>(h, m.data(), 1, 1, h->tick_z, kZW, 7));
         for (int64_t i = 0; i < h->B; ++i) accepted[i] = m[(size_t)i] != 0.0 ? 1 : 0;
     }
     return QLE_OK;
@@ -743,7 +707,7 @@ extern "C" int qle_innovation(qle_batch* h, const double* z, const uint8_t* mask
     QLE_TRY(need_state(h));
     if (!z) return fail(QLE_ERR_INVALID, "z is null");
     QLE_TRY(innov_alloc(h));
-    QLE_TRY(BY_DTYPE(h, pack_z, h, z, mask, h->tick_z));
+    QLE_TRY(BY_DTYPE(h, stage_z, h, z, mask, h->tick_z));
     QLE_TRY(BY_DTYPE(h, launch_innov, h, h->tick_z, false, 0.0));
     if (!nu && !S && !nis) return QLE_OK;   // outputs stay on the device (asynchronous)
     QLE_GUARD_BEGIN
@@ -758,7 +722,7 @@ extern "C" int qle_update_gated(qle_batch* h, const double* z, const uint8_t* ma
     if (!z) return fail(QLE_ERR_INVALID, "z is null");
     QLE_TRY(check_gate(h, chi2_max));
     QLE_TRY(innov_alloc(h));
-    QLE_TRY(BY_DTYPE(h, pack_z, h, z, mask, h->tick_z));
+    QLE_TRY(BY_DTYPE(h, stage_z, h, z, mask, h->tick_z));
     QLE_TRY(BY_DTYPE(h, launch_innov, h, h->tick_z, true, chi2_max));
     h->hist_dirty = true;
     QLE_TRY(BY_DTYPE(h, launch_update, h, h->tick_z));
@@ -777,8 +741,8 @@ extern "C" int qle_step_gated(qle_batch* h, const double* u, const double* z, co
     if (!u || !z) return fail(QLE_ERR_INVALID, "u and z must be non-null");
     QLE_TRY(check_gate(h, chi2_max));
     QLE_TRY(innov_alloc(h));
-    QLE_TRY(BY_DTYPE(h, pack_rows, h, u, kUW, kUW, h->tick_u, kUW, 0));
-    QLE_TRY(BY_DTYPE(h, pack_z, h, z, mask, h->tick_z));
+    QLE_TRY(BY_DTYPE(h, stage_rows, h, u, kUW, kUW, h->tick_u, kUW, 0));
+    QLE_TRY(BY_DTYPE(h, stage_z, h, z, mask, h->tick_z));
     QLE_TRY(BY_DTYPE(h, launch_predict, h, h->tick_u));
     QLE_TRY(BY_DTYPE(h, launch_innov, h, h->tick_z, true, chi2_max));
     QLE_TRY(BY_DTYPE(h, launch_update, h, h->tick_z));
@@ -794,19 +758,9 @@ extern "C" int qle_enable_gating(qle_batch* h, int32_t on)
 {
     QLE_TRY(check_handle(h));
     if (on && !h->last_corr) {
-        int32_t* lc = nullptr;
-        uint8_t* fl = nullptr;
-        hipError_t e = hipMalloc((void**)&lc, sizeof(int32_t) * (size_t)h->Bp);
-        if (e == hipSuccess) e = hipMalloc((void**)&fl, (size_t)h->Bp);
-        if (e == hipSuccess) e = hipMemsetAsync(fl, 0, (size_t)h->Bp, h->stream);
-        if (e != hipSuccess) {
-            if (lc) (void)hipFree(lc);
-            if (fl) (void)hipFree(fl);
-            return fail(QLE_ERR_NOMEM, "gating arrays: %s", hipGetErrorString(e));
-        }
-        h->last_corr = lc; h->flags = fl;
-        // upds_since_correction = 0 before the next tick (EKF.cpp:77): as if tick-1 had corrected
-        QLE_TRY(launch(h, k_fill_i32<int32_t>, grid_for(h, 256), dim3(256), 0, h->last_corr, (int32_t)(h->tick - 1), h->B));
+        hipError_t e = h->mem.acquire({{h->last_corr, sizeof(int32_t) * (size_t)h->Bp}, {h->flags, (size_t)h->Bp, true}}, h->stream);
+        if (e != hipSuccess) return fail(QLE_ERR_NOMEM, "gating arrays: %s", hipGetErrorString(e));
+        QLE_TRY(seed_prev_tick(h, h->last_corr));
     }
     h->gating = on != 0;
     return QLE_OK;
@@ -916,21 +870,14 @@ extern "C" int qle_get_tick_flags(qle_batch* h, uint8_t* performed_correction, u
     QLE_GUARD_BEGIN
     std::vector<uint8_t> f((size_t)h->B);
     HIP_TRY(hipMemcpyAsync(f.data(), h->flags, (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
-    if (upds_since_correction) {   // EKF.cpp:292-299; staged in chunks of the AoS staging buffer
-        int32_t* d_out = reinterpret_cast<int32_t*>(h->stage);
-        if ((size_t)h->B * sizeof(int32_t) <= (size_t)kStageDoubles * sizeof(double)) {
-            QLE_TRY(BY_DTYPE(h, upds_since_t, h, d_out));
-            HIP_TRY(hipMemcpyAsync(upds_since_correction, d_out, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, h->stream));
-        } else {
-            int32_t* tmp = nullptr;
-            HIP_TRY(hipMalloc((void**)&tmp, sizeof(int32_t) * (size_t)h->B));
-            int rc = BY_DTYPE(h, upds_since_t, h, tmp);
-            hipError_t e = rc == QLE_OK ? hipMemcpyAsync(upds_since_correction, tmp, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            (void)hipFree(tmp);
-            if (rc != QLE_OK) return rc;
-            if (e != hipSuccess) return fail(QLE_ERR_HIP, "tick flags: %s", hipGetErrorString(e));
-        }
+    DeviceMem own;   // holds the counters of a batch too large for the staging buffer until the stream has been waited for
+    int32_t* big = nullptr;
+    if (upds_since_correction) {   // EKF.cpp:292-299, through the AoS staging buffer
+        const size_t bytes = sizeof(int32_t) * (size_t)h->B;
+        if (bytes > (size_t)kStageDoubles * sizeof(double)) HIP_TRY(own.acquire({{big, bytes}}));
+        int32_t* d_out = big ? big : reinterpret_cast<int32_t*>(h->stage);
+        QLE_TRY(BY_DTYPE(h, upds_since_t, h, d_out));
+        HIP_TRY(hipMemcpyAsync(upds_since_correction, d_out, bytes, hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
     // the flag bytes are written by ticks that carry tag poses; after a predict-only tick nothing was performed or consumed
@@ -956,7 +903,7 @@ extern "C" int qle_initialize_state_masked(qle_batch* h, const double* z, const 
 {
     QLE_TRY(check_handle(h));
     if (!z) return fail(QLE_ERR_INVALID, "z is null");
-    QLE_TRY(BY_DTYPE(h, pack_z, h, z, mask, h->tick_z));
+    QLE_TRY(BY_DTYPE(h, stage_z, h, z, mask, h->tick_z));
     QLE_TRY(BY_DTYPE(h, seed_t, h, h->tick_z, reinit_bias));
     h->state_set = true;
     return QLE_OK;
@@ -971,7 +918,7 @@ extern "C" int qle_get_state_initialized(qle_batch* h, uint8_t* state_initialize
     if (!state_initialized) return fail(QLE_ERR_INVALID, "output is null");
     QLE_GUARD_BEGIN
     std::vector<double> x((size_t)h->B * kXW);
-    QLE_TRY(BY_DTYPE(h, unpack_rows, h, state_cur(h), kXW, kXW, x.data(), kSW, 0));
+    QLE_TRY(BY_DTYPE(h, stage_rows, h, x.data(), kXW, kXW, state_cur(h), kSW, 0));
     for (int64_t i = 0; i < h->B; ++i) {
         const double* q = &x[(size_t)i * kXW + 6];
         state_initialized[i] = (q[0] != 0.0 || q[1] != 0.0 || q[2] != 0.0 || q[3] != 0.0) ? 1 : 0;
@@ -985,21 +932,19 @@ template <typename T>
 static int report_t(qle_batch* h, double* pose, double* cov, double* vel, double* bias)
 {
     // staged per chunk: 7 + 36 + 3 + 6 = 52 doubles per filter
-    for (int64_t i0 = 0; i0 < h->B; i0 += kStageFilters) {
-        const int64_t n = std::min(kStageFilters, h->B - i0);
-        double* s_pose = h->stage;
-        double* s_cov = s_pose + n * 7;
-        double* s_vel = s_cov + n * 36;
-        double* s_bias = s_vel + n * 3;
-        QLE_TRY(launch(h, k_report_off<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, dev<T>(h), (const T*)state_cur(h),
-                       h->pfp_on ? (const T*)h->pfp : (const T*)nullptr, s_pose, s_cov, s_vel, s_bias, i0, n));
-        if (pose) HIP_TRY(hipMemcpyAsync(pose + i0 * 7, s_pose, (size_t)n * 7 * 8, hipMemcpyDeviceToHost, h->stream));
-        if (cov) HIP_TRY(hipMemcpyAsync(cov + i0 * 36, s_cov, (size_t)n * 36 * 8, hipMemcpyDeviceToHost, h->stream));
-        if (vel) HIP_TRY(hipMemcpyAsync(vel + i0 * 3, s_vel, (size_t)n * 3 * 8, hipMemcpyDeviceToHost, h->stream));
-        if (bias) HIP_TRY(hipMemcpyAsync(bias + i0 * 6, s_bias, (size_t)n * 6 * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return QLE_OK;
+    const auto at = [&](int64_t n, int words_before) { return h->stage + n * words_before; };
+    return for_chunks(
+        h, kStageFilters, false,
+        [&](int64_t i0, int64_t n) -> int {
+            QLE_TRY(stage_copy(h, pose, i0 * 7, at(n, 0), (size_t)n * 7 * 8));
+            QLE_TRY(stage_copy(h, cov, i0 * 36, at(n, 7), (size_t)n * 36 * 8));
+            QLE_TRY(stage_copy(h, vel, i0 * 3, at(n, 43), (size_t)n * 3 * 8));
+            return stage_copy(h, bias, i0 * 6, at(n, 46), (size_t)n * 6 * 8);
+        },
+        [&](int64_t i0, int64_t n) {
+            return launch(h, k_report_off<T>, grid256(n), dim3(256), 0, dev<T>(h), (const T*)state_cur(h), h->pfp_on ? (const T*)h->pfp : (const T*)nullptr, at(n, 0),
+                          at(n, 7), at(n, 43), at(n, 46), i0, n);
+        });
 }
 extern "C" int qle_get_report(qle_batch* h, double* pose, double* pose_cov, double* vel, double* bias)
 {
@@ -1010,7 +955,7 @@ extern "C" int qle_get_report(qle_batch* h, double* pose, double* pose_cov, doub
 template <typename T>
 static int nonfinite_t(qle_batch* h)
 {
-    return launch(h, k_count_nonfinite<T>, grid_for(h, 256), dim3(256), 0, (const T*)state_cur(h), h->counter, h->B, h->compact ? kXW + kPWc : kXW + kPW);
+    return launch(h, k_count_nonfinite<T>, grid_for(h, 256), dim3(256), 0, (const T*)state_cur(h), h->counter, h->B, record_words(h));
 }
 extern "C" int qle_count_nonfinite(qle_batch* h, int64_t* count)
 {
@@ -1032,10 +977,7 @@ extern "C" int qle_inputs_destroy(qle_inputs* in)
 {
     if (!in) return QLE_OK;
     (void)hipSetDevice(in->device);
-    void* bufs[] = {in->u, in->z, in->truth, in->truth_bias, in->d_slot};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    delete in;
+    delete in;   // in->mem frees the device buffers
     return QLE_OK;
 }
 
@@ -1060,11 +1002,8 @@ extern "C" int qle_inputs_create(qle_batch* h, int64_t n_ticks, const uint8_t* t
         if (tick_has_meas && tick_has_meas[t]) in->slot[(size_t)t] = (int32_t)in->n_slots++;
     in->pitch_u = align_up(kUW * (size_t)h->Bp * h->wsz, 256);
     in->pitch_z = align_up(kZW * (size_t)h->Bp * h->wsz, 256);
-    hipError_t e = hipMalloc(&in->u, in->pitch_u * (size_t)n_ticks);
-    if (e == hipSuccess && in->n_slots) e = hipMalloc(&in->z, in->pitch_z * (size_t)in->n_slots);
-    if (e == hipSuccess) e = hipMalloc(&in->truth, (size_t)h->B * 7 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&in->truth_bias, (size_t)h->B * 6 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&in->d_slot, sizeof(int32_t) * (size_t)n_ticks);
+    hipError_t e = in->mem.acquire({{in->u, in->pitch_u * (size_t)n_ticks}, {in->z, in->pitch_z * (size_t)in->n_slots}, {in->truth, (size_t)h->B * 7 * sizeof(double)},
+                                    {in->truth_bias, (size_t)h->B * 6 * sizeof(double)}, {in->d_slot, sizeof(int32_t) * (size_t)n_ticks}});
     if (e == hipSuccess) e = hipMemcpy(in->d_slot, in->slot.data(), sizeof(int32_t) * (size_t)n_ticks, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         qle_inputs_destroy(in);
@@ -1074,6 +1013,7 @@ extern "C" int qle_inputs_create(qle_batch* h, int64_t n_ticks, const uint8_t* t
     return QLE_OK;
 }
 
+static int check_inputs(const qle_batch* h, const qle_inputs* in) { return in && in->h == h ? QLE_OK : fail(QLE_ERR_INVALID, "inputs do not belong to this handle"); }
 static int check_tick(const qle_inputs* in, int64_t t)
 {
     if (!in) return fail(QLE_ERR_INVALID, "inputs is null");
@@ -1089,37 +1029,25 @@ extern "C" int qle_inputs_upload_tick(qle_inputs* in, int64_t t, const double* u
     qle_batch* h = in->h;
     QLE_TRY(check_handle(h));
     if (!u) return fail(QLE_ERR_INVALID, "u is null");
-    QLE_TRY(BY_DTYPE(h, pack_rows, h, u, kUW, kUW, u_at(in, t), kUW, 0));
+    QLE_TRY(BY_DTYPE(h, stage_rows, h, u, kUW, kUW, u_at(in, t), kUW, 0));
     const int32_t s = in->slot[(size_t)t];
     if (s >= 0) {
         if (!z) return fail(QLE_ERR_INVALID, "tick %lld has a measurement slot but z is null", (long long)t);
-        QLE_TRY(BY_DTYPE(h, pack_z, h, z, mask, z_at(in, s)));
+        QLE_TRY(BY_DTYPE(h, stage_z, h, z, mask, z_at(in, s)));
     } else if (z) {
         return fail(QLE_ERR_INVALID, "tick %lld has no measurement slot", (long long)t);
     }
     return QLE_OK;
 }
 
-template <typename T>
-static int unpack_z(qle_batch* h, const void* src, double* z, uint8_t* mask)
-{
-    for (int64_t i0 = 0; i0 < h->B; i0 += kStageFilters) {
-        const int64_t n = std::min(kStageFilters, h->B - i0);
-        QLE_TRY(launch(h, k_unpack_z_off<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const T*)src, h->stage, h->stage_mask, i0, n));
-        if (z) HIP_TRY(hipMemcpyAsync(z + i0 * 7, h->stage, (size_t)n * 7 * 8, hipMemcpyDeviceToHost, h->stream));
-        if (mask) HIP_TRY(hipMemcpyAsync(mask + i0, h->stage_mask, (size_t)n, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return QLE_OK;
-}
 extern "C" int qle_inputs_download_tick(qle_inputs* in, int64_t t, double* u, double* z, uint8_t* mask)
 {
     QLE_TRY(check_tick(in, t));
     qle_batch* h = in->h;
     QLE_TRY(check_handle(h));
-    if (u) QLE_TRY(BY_DTYPE(h, unpack_rows, h, u_at(in, t), kUW, kUW, u, kUW, 0));
+    if (u) QLE_TRY(BY_DTYPE(h, stage_rows, h, u, kUW, kUW, u_at(in, t), kUW, 0));
     const int32_t s = in->slot[(size_t)t];
-    if (s >= 0 && (z || mask)) QLE_TRY(BY_DTYPE(h, unpack_z, h, z_at(in, s), z, mask));
+    if (s >= 0 && (z || mask)) QLE_TRY(BY_DTYPE(h, stage_z, h, z, mask, z_at(in, s)));
     if (s < 0 && mask) std::memset(mask, 0, (size_t)h->B);
     return QLE_OK;
 }
@@ -1128,7 +1056,7 @@ extern "C" int qle_run(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n
 {
     QLE_TRY(check_handle(h));
     QLE_TRY(need_state(h));
-    if (!in || in->h != h) return fail(QLE_ERR_INVALID, "inputs do not belong to this handle");
+    QLE_TRY(check_inputs(h, in));
     if (t0 < 0 || n < 0) return fail(QLE_ERR_INVALID, "t0 and n must be >= 0");
     for (int64_t k = 0; k < n; ++k) {
         const int64_t t = (t0 + k) % in->T;
@@ -1147,7 +1075,7 @@ extern "C" int qle_run(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n
 extern "C" int qle_initialize_state_slot(qle_batch* h, const qle_inputs* in, int64_t t, int32_t reinit_bias)
 {
     QLE_TRY(check_handle(h));
-    if (!in || in->h != h) return fail(QLE_ERR_INVALID, "inputs do not belong to this handle (another handle or batch size)");
+    QLE_TRY(check_inputs(h, in));
     QLE_TRY(check_tick(in, t));
     const int32_t s = in->slot[(size_t)t];
     if (s < 0) return fail(QLE_ERR_INVALID, "tick %lld has no measurement slot to seed from", (long long)t);
@@ -1171,7 +1099,7 @@ extern "C" int qle_get_device_view(qle_batch* h, qle_device_view* out)
     out->padded_batch = h->Bp;
     out->state = state_cur(h);
     out->state_words = kSW;
-    out->record_words = h->compact ? kXW + kPWc : kXW + kPW;
+    out->record_words = record_words(h);
     out->compact = h->compact ? 1 : 0;
     out->filter_params = h->pfp_on ? h->pfp : nullptr;
     for (int k = 0; k < 3; ++k) {
@@ -1198,7 +1126,7 @@ extern "C" int qle_run_resident(qle_batch* h, const qle_inputs* in, int64_t t0, 
 {
     QLE_TRY(check_handle(h));
     QLE_TRY(need_state(h));
-    if (!in || in->h != h) return fail(QLE_ERR_INVALID, "inputs do not belong to this handle");
+    QLE_TRY(check_inputs(h, in));
     if (t0 < 0 || n < 0) return fail(QLE_ERR_INVALID, "t0 and n must be >= 0");
     if (h->mr || h->gating) return fail(QLE_ERR_STATE, "qle_run_resident covers the single-rate filter with explicit masks (no multirate_ekf, no device gating)");
     if (n == 0) return QLE_OK;
@@ -1246,15 +1174,10 @@ static int synth_t(qle_batch* h, qle_inputs* in, const qle_synth_cfg* c)
     a.pitch_u_words = (int64_t)(in->pitch_u / h->wsz);
     a.pitch_z_words = (int64_t)(in->pitch_z / h->wsz);
     const int32_t* d_slot = in->d_slot;
-    hipError_t e = hipSuccess;
-    {
-        if (c->perturb_filter_params && !h->pfp) e = hipMalloc(&h->pfp, kFW * (size_t)h->Bp * h->wsz);
-    }
-    if (e != hipSuccess) return fail(QLE_ERR_HIP, "synthetic generator: %s", hipGetErrorString(e));
+    if (c->perturb_filter_params) QLE_TRY(need_pfp(h));
     QLE_TRY(launch(h, k_synth<T>, grid_for(h, 64), dim3(64), 0, a, (const int32_t*)d_slot, (T*)in->u, (T*)in->z, (T*)h->tick_z,
                    c->perturb_filter_params ? (T*)h->pfp : (T*)nullptr, (double*)in->truth, (double*)in->truth_bias));
-    e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(QLE_ERR_HIP, "synthetic generator: %s", hipGetErrorString(e));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     if (c->perturb_filter_params) h->pfp_on = true;
     in->has_truth = true;
     return QLE_OK;
@@ -1263,7 +1186,7 @@ static int synth_t(qle_batch* h, qle_inputs* in, const qle_synth_cfg* c)
 extern "C" int qle_synth_generate(qle_batch* h, qle_inputs* in, const qle_synth_cfg* c)
 {
     QLE_TRY(check_handle(h));
-    if (!in || in->h != h) return fail(QLE_ERR_INVALID, "inputs do not belong to this handle");
+    QLE_TRY(check_inputs(h, in));
     if (!c) return fail(QLE_ERR_INVALID, "cfg is null");
     QLE_TRY(BY_DTYPE(h, synth_t, h, in, c));
     // seed every filter from the generator's first (pre-sequence) tag pose, left in tick_z
@@ -1275,7 +1198,7 @@ extern "C" int qle_synth_generate(qle_batch* h, qle_inputs* in, const qle_synth_
 extern "C" int qle_synth_get_truth(qle_batch* h, const qle_inputs* in, double* pose, double* imu_bias)
 {
     QLE_TRY(check_handle(h));
-    if (!in || in->h != h) return fail(QLE_ERR_INVALID, "inputs do not belong to this handle");
+    QLE_TRY(check_inputs(h, in));
     if (!in->has_truth) return fail(QLE_ERR_STATE, "inputs hold no generated truth (qle_synth_generate)");
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (pose) HIP_TRY(hipMemcpy(pose, in->truth, (size_t)h->B * 7 * sizeof(double), hipMemcpyDeviceToHost));
@@ -1291,7 +1214,8 @@ static int rmse_t(qle_batch* h, const qle_inputs* in, double* d_out)
 extern "C" int qle_synth_rmse(qle_batch* h, const qle_inputs* in, double out[3])
 {
     QLE_TRY(check_handle(h));
-    if (!in || in->h != h || !out) return fail(QLE_ERR_INVALID, "bad arguments");
+    QLE_TRY(check_inputs(h, in));
+    if (!out) return fail(QLE_ERR_INVALID, "out is null");
     if (!in->has_truth) return fail(QLE_ERR_STATE, "inputs hold no generated truth (qle_synth_generate)");
     double* d_out = h->stage;  // 3 doubles of the staging buffer
     HIP_TRY(hipMemsetAsync(d_out, 0, 3 * sizeof(double), h->stream));

@@ -20,6 +20,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "device_mem.hpp"
 #include "ekf_gate.hpp"
 #include "ekf_layout.hpp"
 #include "ekf_params.hpp"
@@ -29,17 +30,7 @@ using namespace qle;
 // ------------------------------------------------------------------ errors
 
 int qle_fail(int code, const char* fmt, ...);   // sets the thread-local message (ekf_capi.hip), returns code
-#define fail qle_fail
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return fail(QLE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-#define QLE_TRY(expr)            \
-    do {                         \
-        int rc_ = (expr);        \
-        if (rc_ != QLE_OK) return rc_; \
-    } while (0)
+#define fail qle_fail   // what HIP_TRY (device_mem.hpp) returns through
 
 // Nothing may throw across the C ABI: entry points that allocate host memory run under this guard.
 #define QLE_GUARD_BEGIN try {
@@ -113,9 +104,10 @@ struct qle_batch {
     // kernels whose dynamic-LDS limit this handle has raised on its device (launch() below); the oldest entry makes room
     const void* lds_raised[8] = {};
     int32_t lds_next = 0;
+    DeviceMem mem;                 // owns every device buffer the pointers above name; qle_destroy frees what it holds
 };
 
-struct qle_inputs {
+struct __attribute__((visibility("hidden"))) qle_inputs {   // its destructor frees device memory: not for export
     qle_batch* h = nullptr;  // owner; only dereferenced by calls that also take the handle or run before its destroy
     int32_t device = 0;      // copied so that destroy never touches the (possibly already destroyed) handle
     int64_t T = 0;
@@ -128,6 +120,7 @@ struct qle_inputs {
     void* truth_bias = nullptr; // AoS [B][6] fp64
     int32_t* d_slot = nullptr;  // the slot table on the device (qle_run_resident, generator)
     bool has_truth = false;
+    DeviceMem mem;              // owns the five buffers above
 };
 
 static constexpr int64_t kStageFilters = 32768;
@@ -140,6 +133,8 @@ template <> const DevParams<double>& dev<double>(const qle_batch* h) { return h-
 static inline dim3 grid_for(const qle_batch* h, int block) { return dim3((unsigned)((h->B + block - 1) / block)); }
 
 static inline size_t slot_bytes(const qle_batch* h) { return (size_t)kSW * (size_t)h->Bp * h->wsz; }
+// the words of a record that hold values: x and the packed P, or its 9 x 9 pose block alone in compact records
+static inline int record_words(const qle_batch* h) { return h->compact ? kXW + kPWc : kXW + kPW; }
 // the state: one record array, updated in place by every tick
 static inline void* state_cur(const qle_batch* h) { return h->ring; }
 
@@ -158,7 +153,10 @@ static inline int effective_nt(const qle_batch* h)
 }
 
 // Workgroup-cooperative tick kernel (ekf_quad_kernels.hpp): the single-rate tick in place, one 256-thread workgroup per tile.
-static inline bool use_quad(const qle_batch* h, int bit) { return (h->quad & bit) != 0 && !h->mr && !h->compact; }
+// use_quad: for a filter tick.  use_quad_bare: for a bare prediction_step (qle_predict), which neither reads nor extends the multirate
+// history -- the multirate flag does not apply to it.
+static inline bool use_quad_bare(const qle_batch* h, int bit) { return (h->quad & bit) != 0 && !h->compact; }
+static inline bool use_quad(const qle_batch* h, int bit) { return use_quad_bare(h, bit) && !h->mr; }
 
 static inline GateParams make_gate(const qle_batch* h)
 {

@@ -106,18 +106,14 @@ extern "C" int qhl_health_host(const qle_device_view* view, const qhl_limits* li
     QLE_TRY(use_device(view));
     hipStream_t s = (hipStream_t)view->stream;
     const size_t B = (size_t)view->batch;
-    Staging<4> d;
-    if (mask) {
-        HIP_TRY(hipMalloc(&d.p[0], B));
-        HIP_TRY(hipMemcpyAsync(d.p[0], mask, B, hipMemcpyHostToDevice, s));
-    }
-    if (status) HIP_TRY(hipMalloc(&d.p[1], B));
-    if (flagged) HIP_TRY(hipMalloc(&d.p[2], B));
-    if (summary) HIP_TRY(hipMalloc(&d.p[3], sizeof(qhl_summary)));
-    QLE_TRY(qhl_health(view, limits, (const uint8_t*)d.p[0], (uint8_t*)d.p[1], (uint8_t*)d.p[2], (qhl_summary*)d.p[3]));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d.p[1], B, hipMemcpyDeviceToHost, s));
-    if (flagged) HIP_TRY(hipMemcpyAsync(flagged, d.p[2], B, hipMemcpyDeviceToHost, s));
-    if (summary) HIP_TRY(hipMemcpyAsync(summary, d.p[3], sizeof(qhl_summary), hipMemcpyDeviceToHost, s));
+    DeviceMem own;
+    void* d[4] = {};
+    HIP_TRY(own.acquire({{d[0], mask ? B : 0}, {d[1], status ? B : 0}, {d[2], flagged ? B : 0}, {d[3], summary ? sizeof(qhl_summary) : 0}}));
+    if (mask) HIP_TRY(hipMemcpyAsync(d[0], mask, B, hipMemcpyHostToDevice, s));
+    QLE_TRY(qhl_health(view, limits, (const uint8_t*)d[0], (uint8_t*)d[1], (uint8_t*)d[2], (qhl_summary*)d[3]));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d[1], B, hipMemcpyDeviceToHost, s));
+    if (flagged) HIP_TRY(hipMemcpyAsync(flagged, d[2], B, hipMemcpyDeviceToHost, s));
+    if (summary) HIP_TRY(hipMemcpyAsync(summary, d[3], sizeof(qhl_summary), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return QLE_OK;
 }

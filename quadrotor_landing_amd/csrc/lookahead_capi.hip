@@ -110,16 +110,13 @@ extern "C" int qlk_lookahead_host(const qle_device_view* view, const qle_params*
     QLE_TRY(use_device(view));
     hipStream_t s = (hipStream_t)view->stream;
     const size_t B = (size_t)view->batch;
-    Staging<3> d;
-    HIP_TRY(hipMalloc(&d.p[0], B * kUW * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(d.p[0], u, B * kUW * sizeof(double), hipMemcpyHostToDevice, s));
-    if (mask) {
-        HIP_TRY(hipMalloc(&d.p[1], B));
-        HIP_TRY(hipMemcpyAsync(d.p[1], mask, B, hipMemcpyHostToDevice, s));
-    }
-    if (ticks_to_limit) HIP_TRY(hipMalloc(&d.p[2], B * sizeof(int32_t)));
-    QLE_TRY(run(view, params, der, Call{d.p[0], 1, h, (const uint8_t*)d.p[1], workspace, lim, (int32_t*)d.p[2]}, ahead));
-    if (ticks_to_limit) HIP_TRY(hipMemcpyAsync(ticks_to_limit, d.p[2], B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    DeviceMem own;
+    void* d[3] = {};
+    HIP_TRY(own.acquire({{d[0], B * kUW * sizeof(double)}, {d[1], mask ? B : 0}, {d[2], ticks_to_limit ? B * sizeof(int32_t) : 0}}));
+    HIP_TRY(hipMemcpyAsync(d[0], u, B * kUW * sizeof(double), hipMemcpyHostToDevice, s));
+    if (mask) HIP_TRY(hipMemcpyAsync(d[1], mask, B, hipMemcpyHostToDevice, s));
+    QLE_TRY(run(view, params, der, Call{d[0], 1, h, (const uint8_t*)d[1], workspace, lim, (int32_t*)d[2]}, ahead));
+    if (ticks_to_limit) HIP_TRY(hipMemcpyAsync(ticks_to_limit, d[2], B * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return QLE_OK;
 }

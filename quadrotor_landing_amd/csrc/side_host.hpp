@@ -17,6 +17,7 @@
 #include <utility>
 
 #include "../../include/qle_ekf.h"
+#include "device_mem.hpp"
 #include "ekf_layout.hpp"
 
 namespace qle {
@@ -36,16 +37,6 @@ int fail(int code, const char* fmt, ...)
     g_err = buf;
     return code;
 }
-#define HIP_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(QLE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-#define QLE_TRY(expr)                  \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != QLE_OK) return rc_; \
-    } while (0)
 // the two diagnostics entries of a library's header, over the library's own copies of the string and the counter
 #define QLE_SIDE_LAST_ERROR(name) extern "C" const char* name(void) { return qle::side::g_err.c_str(); }
 #define QLE_SIDE_LAUNCH_COUNT(name) extern "C" int64_t name(void) { return qle::side::g_launches.load(std::memory_order_relaxed); }
@@ -97,15 +88,9 @@ void with(bool b, F&& f)
     else f(std::false_type{});
 }
 
-// device buffers of one *_host call, freed however the call ends
-template <int N>
-struct Staging {
-    void* p[N] = {};
-    ~Staging() { for (void* q : p) if (q) (void)hipFree(q); }
-};
-
 // The [tiles][sums] partials of a batch summary: one buffer per (device, stream), grown on demand and kept -- two calls on one
-// stream are ordered, two streams never share a buffer.
+// stream are ordered, two streams never share a buffer.  A cache for the life of the process, never destroyed: it keeps its own hipMalloc /
+// hipFree instead of a DeviceMem (device_mem.hpp), which is what the device buffers of one *_host call are held by.
 class Partials {
 public:
     explicit Partials(int sums) : sums_(sums) {}

@@ -352,3 +352,50 @@ def test_lifecycle_calls_are_ordered_by_streams_not_by_synchronisation():
     assert np.isfinite(res[0][0]).all() and res[0][0][1] > 0 and res[0][0][0] > 0
     for a, b, what in zip(res[0], res[1], ("reduction", "x", "P")):
         assert_same_bits(a, b, what)
+
+
+# ------------------------------------------------------------------------------------------------ 8. destroy frees what the handle owns
+def test_create_use_close_cycles_return_their_device_memory():
+    """One fp64 handle of 16 384 filters that owns every kind of device buffer a handle can own (state, multirate history, gating
+    arrays, side outputs, per-filter parameters, innovation records, an 8-tick sequence with its generated truth), created, used and
+    closed 25 times, the history replaced once per cycle by parameters that change its checkpoint count.
+
+    F = the device memory the first create takes.  After the 24 further cycles, free memory must be within F / 2 of what it was
+    after the first close: a condition, not a measurement -- one batch-sized buffer class of at least F / 48 leaked per cycle exceeds
+    it.  It assumes that freed device memory returns to the device at once."""
+    t = _torch()
+    B = 16384
+    kw = dict(KW, multirate_ekf=1, dynamic_meas_delay=1, measurement_delay_max=0.2)
+    t.cuda.synchronize()
+    free = lambda: t.cuda.mem_get_info(0)[0]
+
+    def cycle(after_create=None):
+        ekf = qla.BatchedRelativePoseEKF(B, "f64", **kw)
+        if after_create is not None:
+            after_create.append(free())
+        rng = np.random.default_rng(80)
+        ekf.enable_gating(True); ekf.enable_aux(True)
+        seq = ekf.make_inputs(8, [0, 0, 0, 1, 0, 0, 0, 1])
+        ekf.synth_generate(seq, seed=0xE4F00005)
+        ekf.set_filter_params(np.tile(np.concatenate([list(ekf.derived.Q), KW["ab_static"], KW["wb_static"], list(ekf.derived.R)]), (B, 1)))
+        ekf.innovation(rand_pose(rng, B))
+        ekf.run(seq, 0, 8)
+        slots = ekf.policy()["ring_slots"]
+        ekf.initialize_params(measurement_delay_max=0.4)        # another checkpoint count: the six history buffers are replaced
+        assert ekf.policy()["ring_slots"] != slots
+        ekf.run(seq, 0, 8)
+        assert ekf.count_nonfinite() == 0
+        seq.close(); ekf.close()
+
+    before = free()
+    created = []
+    cycle(created)
+    F = before - created[0]
+    first_close = free()
+    for _ in range(24):
+        cycle()
+    end = free()
+    print(f"leak check: F = {F / 2**20:.1f} MiB; free before {before / 2**20:.1f}, after the first close {first_close / 2**20:.1f}, "
+          f"after 24 more cycles {end / 2**20:.1f} MiB")
+    assert F > 0
+    assert abs(first_close - end) <= F / 2, (F, before, first_close, end)
