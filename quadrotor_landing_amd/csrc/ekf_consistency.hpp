@@ -15,8 +15,8 @@
 //   marginal   no second code path: for an unselected state j, e_j = 0, P_jj = 1 and row and column j of P are zero, and the full matrix
 //              is factored; the quadratic form of the result is exactly the marginal's.  `blocks` is wave-uniform: selects, no branch
 //   factor     P = L D L^T in place on the packed words (sidx, compile-time indices), y = L^-1 e carried along, NEES = sum y_m^2 / d_m
-//              -- the scheme of the 6 x 6 factor of pregate_eval.  A pivot <= 0 (or NaN): NEES = NaN, the filter is flagged not
-//              positive definite
+//              -- ldl_solve of ekf_device.hpp, the routine of the 6 x 6 factor of pregate_eval.  A pivot <= 0 (or NaN): NEES = NaN, the
+//              filter is flagged not positive definite
 //   stores     nees [B], err [B][n] in the destination dtype, and eight fp64 partial sums per 64-filter tile
 // Words moved per filter: full records 16 + 120 + 16 (truth) in, 1 + n out: 168 with every output, 153 with nees alone; compact records
 // 16 + 48 + 16 in: 90 / 81.  Per-filter parameters add the two quad rows (fp32) or four (fp64) that hold the static biases.
@@ -46,31 +46,6 @@ __host__ __device__ constexpr int nees_dof(uint32_t blocks)
     int n = 0;
     for (int b = 0; b < 5; ++b) n += (blocks >> b) & 1u ? 3 : 0;
     return n;
-}
-
-// P = L D L^T of the leading N x N block, in place on the packed words (the pivots d_m are left on the diagonal).  RHS: y = L^-1 y is
-// carried along and the quadratic form sum y_m^2 / d_m returned (0 without).  Returns in pd whether every pivot is > 0 (a NaN pivot is
-// not).  The one factorisation of the read-only diagnostics: k_nees (nees_eval below) and k_health (ekf_health.hpp) both call it.
-template <typename T, int N, bool RHS>
-__device__ __forceinline__ T ldl_factor(T (&P)[120], T (&y)[N], bool& pd)
-{
-    T quad = T(0);
-    pd = true;
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        const T d = P[sidx(c, c)];
-        pd = pd && d > T(0);
-        const T inv = T(1) / d;
-#pragma unroll
-        for (int j = c + 1; j < N; ++j) {
-            const T l = P[sidx(c, j)] * inv;
-#pragma unroll
-            for (int j2 = j; j2 < N; ++j2) P[sidx(j, j2)] -= l * P[sidx(c, j2)];
-            if constexpr (RHS) y[j] -= l * y[c];
-        }
-        if constexpr (RHS) quad += y[c] * y[c] * inv;
-    }
-    return quad;
 }
 
 // e = truth (-) estimate (15 words: r, v, th, ab, wb) of state x against truth row xt (r, v, q xyzw, ab, wb; the TOTAL biases) and the
@@ -119,16 +94,14 @@ __device__ __forceinline__ T nees_eval(const T (&x)[16], T (&P)[120], const T (&
         }
     }
     // P = L D L^T in place, y = L^-1 e carried along: NEES = sum y_m^2 / d_m
-    const T nees = ldl_factor<T, N, true>(P, y, pd);
+    const T nees = ldl_solve<N, true>([&](int i, int j) -> T& { return P[sidx(i, j)]; }, y, pd);
     return pd ? nees : T(NAN);
 }
 
 }  // namespace qle
 
-// (ekf_health.hpp takes ldl_factor from this header and none of its kernels: QLE_CONSISTENCY_NO_KERNELS)
-#if defined(__HIPCC__) && !defined(QLE_CONSISTENCY_NO_KERNELS)
+#if defined(__HIPCC__)
 #include "ekf_layout.hpp"
-#include "ekf_pregate.hpp"   // load_rec_cached, put
 
 namespace qle {
 
@@ -169,7 +142,7 @@ __global__ __launch_bounds__(kTile, sizeof(T) == 8 ? 1 : 2) void k_nees(const T*
     const int64_t i = (int64_t)blockIdx.x * kTile + threadIdx.x;   // the records are allocated for whole tiles: every lane may load
     const int64_t row = i < B ? i : B - 1;                          // the tensors are not: the lanes beyond the end read the last row
     T x[kXW], P[kPW], t[16];
-    load_rec_cached<T, kSW, kXW>(st, i, x);
+    load_rec<T, kSW, 0, kXW>(st, i, x);
     if constexpr (COMPACT) load_P_compact<T>(st, i, P);
     else load_rec<T, kSW, kXW, kPW>(st, i, P);
     load_truth<T>(xt, row, true_f64 != 0, t);
@@ -207,22 +180,12 @@ __global__ __launch_bounds__(kTile, sizeof(T) == 8 ? 1 : 2) void k_nees(const T*
     }
 }
 
-// One workgroup: the tiles' partials in a fixed order into the eight doubles of a qcs_summary.  Thread t adds field t % 8 of the tiles
-// t / 8, t / 8 + 32, ... in ascending order; threads 0..7 then add the 32 slices in ascending order.  dof is not a sum.
+// One workgroup: the tiles' partials in a fixed order (reduce_tiles, ekf_layout.hpp) into the eight doubles of a qcs_summary.  dof is
+// not a sum.
 __global__ __launch_bounds__(kBlock) void k_nees_reduce(const double* __restrict__ partials, int64_t tiles, double* __restrict__ summary)
 {
-    __shared__ double part[kBlock];
-    const int f = (int)threadIdx.x & 7, s = (int)threadIdx.x >> 3;
-    double acc = 0.0;
-    for (int64_t k = s; k < tiles; k += kBlock / 8) acc += partials[k * kNeesSums + f];
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x < kNeesSums) {
-        double tot = 0.0;
-        for (int k = 0; k < kBlock / 8; ++k) tot += part[k * 8 + f];
-        summary[f] = f == kNeesSums - 1 ? partials[kNeesSums - 1] : tot;
-    }
+    reduce_tiles<kNeesSums, 8>(partials, tiles, [&](int f, double tot) { summary[f] = f == kNeesSums - 1 ? partials[kNeesSums - 1] : tot; });
 }
 
 }  // namespace qle
-#endif  // __HIPCC__ && !QLE_CONSISTENCY_NO_KERNELS
+#endif  // __HIPCC__

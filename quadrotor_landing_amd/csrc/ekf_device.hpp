@@ -168,6 +168,17 @@ struct Noise {
     T R[6];
 };
 
+// The 16 state words: r (0..2), v (3..5), q xyzw (6..9), ab (10..12), wb (13..15).
+// A filter is "not initialised" (state_initialized == false, EKF.cpp:73,129-130) while its stored quaternion is all
+// zero -- the state memory starts zeroed, initialize_state / set_state write a unit quaternion -- and every tick kernel
+// leaves such a filter untouched: no predict, no counters, no history entry, exactly the reference's early return.
+// The flag lives in the record the tick reads anyway, so it costs no traffic.
+template <typename T>
+__host__ __device__ __forceinline__ bool filter_uninitialised(const T (&x)[16])
+{
+    return x[6] == T(0) && x[7] == T(0) && x[8] == T(0) && x[9] == T(0);
+}
+
 // sin(h) / (2 h) and cos(h): the vector scale and the scalar part of exp(phi), h = |phi| / 2 (QH.cpp:9-28).  Series in h^2 on
 // |h| <= pi/4 (truncation < 3e-10 in fp32, < 3e-20 in fp64).  Larger half-angles (no physical rate: more than 90 degrees per tick) are
 // halved until they fit and the result is doubled back -- sin 2a / 2a = (sin a / a) cos a, cos 2a = 1 - 2 a^2 (sin a / a)^2, no square
@@ -974,6 +985,35 @@ __device__ __forceinline__ void ekf_update(const DevParams<T>& p, const Noise<T>
 #pragma unroll
         for (int k = 0; k < 7; ++k) obs[k] = o[k];
     });
+}
+
+// ------------------------------------------------------- read-only diagnostics
+// A = L D L^T of a symmetric N x N matrix, in place on its upper triangle: at(i, j), i <= j, names the element (the pivots d_m are
+// left on the diagonal).  RHS: y = L^-1 y is carried along and the quadratic form sum y_m^2 / d_m returned (0 without).  Returns in pd
+// whether every pivot is > 0 (a NaN pivot is not).  The one factorisation of the side libraries' read-only diagnostics: k_nees
+// (ekf_consistency.hpp) and k_health (ekf_health.hpp) call it on the packed covariance, k_pregate (ekf_pregate.hpp) on its 6 x 6
+// innovation covariance -- "not positive definite" is one rule in all three.  (k_innov, ekf_innov.hpp, keeps the loop written out, for
+// the reason given there; the fused tick has its own factor, quad::update_factor.)
+template <int N, bool RHS, typename T, typename At>
+__device__ __forceinline__ T ldl_solve(At&& at, T (&y)[N], bool& pd)
+{
+    T quad = T(0);
+    pd = true;
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        const T d = at(c, c);
+        pd = pd && d > T(0);
+        const T inv = T(1) / d;
+#pragma unroll
+        for (int j = c + 1; j < N; ++j) {
+            const T l = at(c, j) * inv;
+#pragma unroll
+            for (int j2 = j; j2 < N; ++j2) at(j, j2) -= l * at(c, j2);
+            if constexpr (RHS) y[j] -= l * y[c];
+        }
+        if constexpr (RHS) quad += y[c] * y[c] * inv;
+    }
+    return quad;
 }
 
 }  // namespace qle

@@ -7,8 +7,8 @@
 //              ekf_layout.hpp (1 KiB-contiguous dwordx4 rows per wave), the mask byte
 //   status     a byte of QHL_* bits per filter, defined on the stored words cast to double (include/qle_health.h):
 //              NONFINITE  any record word is NaN or Inf -- when set, nothing else is evaluated
-//              NOT_PD     a pivot of P = L D L^T over the handle's n x n covariance is <= 0 or not finite: ldl_factor of
-//                         ekf_consistency.hpp, the factorisation (and the rule) under which k_nees counts n_not_pd with every block of the
+//              NOT_PD     a pivot of P = L D L^T over the handle's n x n covariance is <= 0 or not finite: ldl_solve of
+//                         ekf_device.hpp, the factorisation (and the rule) under which k_nees counts n_not_pd with every block of the
 //                         handle selected.  A full record with n = 9 factors its 9 x 9 pose block: k_nees puts the identity into the
 //                         unselected bias blocks, whose pivots are 1 and whose rows change nothing
 //              QNORM      |q.q - 1| > qnorm_tol, the sum ((q0^2 + q1^2) + q2^2) + q3^2 in fp64 without contraction
@@ -30,8 +30,7 @@
 #include <cmath>
 #include <cstdint>
 
-#define QLE_CONSISTENCY_NO_KERNELS   // the factorisation, not k_nees: this library's kernels are its own
-#include "ekf_consistency.hpp"   // ldl_factor
+#include "ekf_device.hpp"
 
 namespace qle {
 
@@ -50,14 +49,14 @@ struct HealthLimits {
 // Status byte of one filter.  x: the 16 state words.  P: the 15-state register image of the packed covariance (factored in place,
 // destroyed).  N: the handle's number of states, 15 or 9; with 9 only the 9 x 9 pose block is factored.  COMPACT: only that block is a
 // record word, the rest of the image is never read.  probe: 0, or NaN when a record word outside x and the image (the padding of a
-// compact covariance) is not finite.  no_state: the stored quaternion is all zero (filter_uninitialised, ekf_layout.hpp) -- the caller
+// compact covariance) is not finite.  no_state: the stored quaternion is all zero (filter_uninitialised, ekf_device.hpp) -- the caller
 // stores status 0 for such a filter.
 template <typename T, bool COMPACT, int N>
 __device__ __forceinline__ uint32_t health_classify(const T (&x)[16], T (&P)[120], T probe, const HealthLimits& lim, bool& no_state)
 {
     static_assert(N == 9 || (N == 15 && !COMPACT), "15 states or 9; compact records hold 9");
     constexpr int NW = COMPACT ? 9 : 15;   // the covariance words of the record: all of them count for NONFINITE
-    no_state = x[6] == T(0) && x[7] == T(0) && x[8] == T(0) && x[9] == T(0);
+    no_state = filter_uninitialised(x);
     // w * 0 is 0 for a finite word and NaN otherwise: one multiply-add per word
 #pragma unroll
     for (int k = 0; k < 16; ++k) probe += x[k] * T(0);
@@ -92,7 +91,7 @@ __device__ __forceinline__ uint32_t health_classify(const T (&x)[16], T (&P)[120
     {   // P = L D L^T over the handle's N states
         T none[N];
         bool pd;
-        (void)ldl_factor<T, N, false>(P, none, pd);
+        (void)ldl_solve<N, false>([&](int i, int j) -> T& { return P[sidx(i, j)]; }, none, pd);
         T pp = T(0);   // the pivots are left on the diagonal: an overflowed one is not a pivot of a positive definite matrix either
 #pragma unroll
         for (int c = 0; c < N; ++c) pp += P[sidx(c, c)] * T(0);
@@ -156,25 +155,14 @@ __global__ __launch_bounds__(kTile, sizeof(T) == 8 ? 1 : 2) void k_health(const 
     if (flagged) flagged[i] = flag ? 1 : 0;
 }
 
-// One workgroup: the tiles' partials in a fixed order into the nine doubles of a qhl_summary.  Thread t adds field t % 16 (< 9) of the
-// tiles t / 16, t / 16 + 16, ... in ascending order; threads 0..8 then add the 16 slices in ascending order.
+// One workgroup: the tiles' partials in a fixed order (reduce_tiles, ekf_layout.hpp; slices of 16 for the nine fields) into the nine
+// doubles of a qhl_summary.
 __global__ __launch_bounds__(kBlock) void k_health_reduce(const double* __restrict__ partials, int64_t tiles, double* __restrict__ summary)
 {
-    __shared__ double part[kBlock];
-    const int f = (int)threadIdx.x & 15, s = (int)threadIdx.x >> 4;
-    double acc = 0.0;
-    if (f < kHealthSums)
-        for (int64_t k = s; k < tiles; k += kBlock / 16) acc += partials[k * kHealthSums + f];
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x < kHealthSums) {
-        double tot = 0.0;
-        for (int k = 0; k < kBlock / 16; ++k) tot += part[k * 16 + f];
-        summary[f] = tot;
-    }
+    reduce_tiles<kHealthSums, 16>(partials, tiles, [&](int f, double tot) { summary[f] = tot; });
 }
 
-// "No state" for the filters with mask[i] != 0: the 16 x words become zero (filter_uninitialised, ekf_layout.hpp), which every tick
+// "No state" for the filters with mask[i] != 0: the 16 x words become zero (filter_uninitialised, ekf_device.hpp), which every tick
 // kernel leaves untouched and a later seed treats as fresh -- and so do the covariance words, so that a retired record is the record of
 // a filter that never had a state (all zero), broken values included.  One lane per filter; compact is wave-uniform.
 template <typename T>

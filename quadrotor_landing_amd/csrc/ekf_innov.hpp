@@ -2,7 +2,9 @@
 //
 // correction_step forms the innovation delta_y (EKF.cpp:447-450) and its covariance S = G P G^T + R_k (EKF.cpp:475) and uses them only
 // inside the gain.  k_innov evaluates them against the current state, one lane per filter, and reads nothing but x, the 21 words of the
-// pose block P_JJ (J = r0..2, th0..2, the only columns G touches), the tag record and the filter's noise.  It never writes the state:
+// pose block P_JJ (J = r0..2, th0..2, the only columns G touches), the tag record and the filter's noise -- as whole 16-byte quad rows
+// (load_P_rows, ekf_layout.hpp) 36 covariance words per filter in fp32 and 30 in fp64, 36 / 26 of a compact record.  It never writes
+// the state:
 //   diagnostics (GATE = false): nu = delta_y (6), S (21, packed upper triangle) into a kDW-word record per filter, and the normalised
 //     innovation squared NIS = delta_y^T S^-1 delta_y into nis[i];
 //   gate (GATE = true): accepted = mask && initialised && isfinite(NIS) && NIS <= chi2_max goes into the mask word of the tag record, so
@@ -17,8 +19,6 @@
 // Every lane runs its own straight-line arithmetic; nothing is decided across the wave.
 #pragma once
 
-#include <utility>
-
 #include "ekf_layout.hpp"
 
 namespace qle {
@@ -26,40 +26,9 @@ namespace qle {
 constexpr int kDW = 28;   // diagnostics record: nu (6), S packed upper triangle (21), 1 pad
 
 __host__ __device__ constexpr int innov_state_col(int a) { return a < 3 ? a : a + 3; }   // J = {0,1,2,6,7,8}
-// does quad row k (VW words) of the packed covariance hold an element of P_JJ?
-__host__ __device__ constexpr bool pose_quad(int k, int vw, bool compact)
-{
-    for (int a = 0; a < 6; ++a)
-        for (int b = a; b < 6; ++b)
-            if ((p_word(innov_state_col(a), innov_state_col(b), compact) - kXW) / vw == k) return true;
-    return false;
-}
 __host__ __device__ constexpr int sidx6(int a, int b) { return a * 6 - a * (a - 1) / 2 + (b - a); }   // a <= b < 6
-
-template <typename T, bool COMPACT, int... K>
-__device__ __forceinline__ void load_pose_quads(const T* __restrict__ tb, int lane, T (&w)[kPW], std::integer_sequence<int, K...>)
-{
-    using Q = typename Quad<T>::type;
-    constexpr int VW = Quad<T>::VW;
-    (..., [&] {
-        if constexpr (pose_quad(K, VW, COMPACT)) unpack_quad(*reinterpret_cast<const Q*>(tb + ((kXW / VW + K) * kTile + lane) * VW), &w[K * VW]);
-    }());
-}
-// P_JJ from either record layout: only the quad rows that hold one of its 21 elements are read.
-template <typename T, bool COMPACT>
-__device__ __forceinline__ void load_P_pose(const T* __restrict__ st, int64_t i, T (&Pj)[6][6])
-{
-    constexpr int VW = Quad<T>::VW;
-    const int64_t tile = wave_tile(i);
-    const int lane = (int)(i & 63);
-    const T* tb = st + tile * (int64_t)(kSW * kTile);
-    T w[kPW];
-    load_pose_quads<T, COMPACT>(tb, lane, w, std::make_integer_sequence<int, kPW / VW>{});
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = a; b < 6; ++b) Pj[a][b] = Pj[b][a] = w[p_word(innov_state_col(a), innov_state_col(b), COMPACT) - kXW];
-}
+static_assert(CovSrc<4, false, pose_needs>{}.words == 36 && CovSrc<2, false, pose_needs>{}.words == 30 && CovSrc<4, true, pose_needs>{}.words == 36 &&
+              CovSrc<2, true, pose_needs>{}.words == 26, "the word counts stated at the top of this file");
 
 // nu, S (packed, a <= b) and NIS of one filter from its decorrelated measurement.
 template <typename T, bool DIRECT>
@@ -126,7 +95,8 @@ __device__ __forceinline__ T innov_from_prep(const UpdatePrep<T>& u, const T (&P
     for (int a = 0; a < 6; ++a)
 #pragma unroll
         for (int b = a; b < 6; ++b) Sp[sidx6(a, b)] = T(0.5) * (S[a][b] + S[b][a]);
-    // NIS = y'^T S'^-1 y' through S' = Ls E Ls^T: the sum of (Ls^-1 y')_c^2 / e_c
+    // NIS = y'^T S'^-1 y' through S' = Ls E Ls^T: the sum of (Ls^-1 y')_c^2 / e_c.  The loop of ldl_solve (ekf_device.hpp), written out:
+    // called through it, 9 of this kernel's 32 instantiations change their register count (one from 128 to 129 VGPRs, an occupancy step).
     T y[6];
 #pragma unroll
     for (int a = 0; a < 6; ++a) y[a] = u.dy[a];
@@ -175,7 +145,14 @@ __global__ __launch_bounds__(kBlock) void k_innov(const T* __restrict__ st, T* _
         return;
     }
     T Pj[6][6];
-    load_P_pose<T, COMPACT>(st, i, Pj);
+    {   // P_JJ out of the register image: only the quad rows that hold one of its 21 elements are read
+        T P[kPW];
+        load_P_rows<T, COMPACT, pose_needs>(st, i, P);
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) Pj[a][b] = Pj[b][a] = P[sidx(innov_state_col(a), innov_state_col(b))];
+    }
     Noise<T> nz;
     load_noise<T, PFP>(p, pfp, i, nz);
     const T z[7] = {zr[0], zr[1], zr[2], zr[3], zr[4], zr[5], zr[6]};

@@ -21,6 +21,7 @@
 #pragma once
 
 #include <type_traits>
+#include <utility>
 
 #include "ekf_device.hpp"
 
@@ -56,7 +57,9 @@ template <> struct Quad<double> { using type = qle_d2; static constexpr int VW =
 // Which accesses of a hot kernel are non-temporal under policy NT (profiles/r01_tuning.md section 5, sustained rates):
 //   IMU / tag records (read once, never again): always non-temporal, so the input stream does not displace the state
 //   in the Infinity Cache; state and per-filter parameter records: loads non-temporal for NT >= 1, stores for NT >= 2.
-template <int NT, int WT> struct NtLd { static constexpr int value = (WT == kUW || WT == kZW || NT >= 1) ? 2 : 0; };
+// kCached in place of NT: cached loads whatever the record is -- for a kernel that is not the last reader of an IMU or tag record.
+constexpr int kCached = -1;
+template <int NT, int WT> struct NtLd { static constexpr int value = NT == kCached ? 0 : (WT == kUW || WT == kZW || NT >= 1) ? 2 : 0; };
 template <int NT> struct NtSt { static constexpr int value = NT >= 2 ? 2 : 0; };
 
 template <int NT, typename Q>
@@ -207,6 +210,61 @@ __device__ __forceinline__ void store_P_any(T* __restrict__ st, int64_t i, const
     else store_rec<T, kSW, kXW, kPW, NT>(st, i, P);
 }
 
+
+// The covariance words a read-only kernel needs, into the 15-state register image.  NEEDS(a, b), a <= b: does the kernel read P(a, b)?
+// Only the 16-byte quad rows that hold a needed word are loaded (whole rows: the image takes every word of a loaded row); the other
+// slots are zero -- never read, or the bias blocks a compact record does not hold.
+using CovNeeds = bool (*)(int, int);
+// the pose block P_JJ, J = r0..2, th0..2: the only columns the measurement Jacobian G touches
+__host__ __device__ constexpr bool pose_needs(int a, int b) { return (a < 3 || (a >= 6 && a < 9)) && (b < 3 || (b >= 6 && b < 9)); }
+// per quad row (VW words) of the packed covariance: is it loaded?  Per slot of the register image: the loaded covariance word it takes,
+// or -1 (zero).  A compile-time table: written as a plain loop over the predicate in the kernel, the selection is not folded and runs
+// on the scalar unit (some 20 000 SALU instructions per wave).
+template <int VW, bool COMPACT, CovNeeds NEEDS>
+struct CovSrc {
+    static constexpr int kRows = (COMPACT ? kPWc : kPW) / VW;
+    bool row[kRows];
+    int w[kPW];
+    int words;   // words of the covariance the kernel moves per filter (whole quad rows)
+    constexpr CovSrc() : row{}, w{}, words(0)
+    {
+        for (int a = 0; a < 15; ++a)
+            for (int b = a; b < 15; ++b) {
+                const int rw = p_word(a, b, COMPACT);
+                if (rw >= 0 && NEEDS(a, b)) row[(rw - kXW) / VW] = true;
+            }
+        for (int k = 0; k < kRows; ++k) words += row[k] ? VW : 0;
+        for (int a = 0; a < 15; ++a)
+            for (int b = a; b < 15; ++b) {
+                const int rw = p_word(a, b, COMPACT);
+                w[sidx(a, b)] = (rw >= 0 && row[(rw - kXW) / VW]) ? rw - kXW : -1;
+            }
+    }
+};
+template <typename T, bool COMPACT, CovNeeds NEEDS, int... K, int... S>
+__device__ __forceinline__ void load_P_rows_seq(const T* __restrict__ tb, int lane, T (&P)[kPW], std::integer_sequence<int, K...>,
+                                                std::integer_sequence<int, S...>)
+{
+    using Q = typename Quad<T>::type;
+    constexpr int VW = Quad<T>::VW;
+    constexpr CovSrc<VW, COMPACT, NEEDS> src{};
+    T w[kPW];
+    (..., [&] {
+        if constexpr (src.row[K]) unpack_quad(*reinterpret_cast<const Q*>(tb + ((kXW / VW + K) * kTile + lane) * VW), &w[K * VW]);
+    }());
+    (..., [&] {
+        if constexpr (src.w[S] >= 0) P[S] = w[src.w[S]];
+        else P[S] = T(0);
+    }());
+}
+template <typename T, bool COMPACT, CovNeeds NEEDS>
+__device__ __forceinline__ void load_P_rows(const T* __restrict__ st, int64_t i, T (&P)[kPW])
+{
+    load_P_rows_seq<T, COMPACT, NEEDS>(st + wave_tile(i) * (int64_t)(kSW * kTile), (int)(i & 63), P,
+                                       std::make_integer_sequence<int, CovSrc<Quad<T>::VW, COMPACT, NEEDS>::kRows>{},
+                                       std::make_integer_sequence<int, kPW>{});
+}
+
 template <typename T, bool PFP>
 __device__ __forceinline__ void load_noise(const DevParams<T>& p, const T* __restrict__ pfp, int64_t i, Noise<T>& nz)
 {
@@ -257,16 +315,6 @@ __device__ __forceinline__ void store_P_quads_desc(T* __restrict__ st, int64_t i
     for (int k = Q1 - 1; k >= Q0; --k) st_quad<NtSt<NT>::value>(reinterpret_cast<Q*>(tb + ((kXW / VW + k) * kTile + lane) * VW), pack_quad(&P[k * VW]));
 }
 
-// A filter is "not initialised" (state_initialized == false, EKF.cpp:73,129-130) while its stored quaternion is all
-// zero -- the state memory starts zeroed, initialize_state / set_state write a unit quaternion -- and every tick kernel
-// leaves such a filter untouched: no predict, no counters, no history entry, exactly the reference's early return.
-// The flag lives in the record the tick reads anyway, so it costs no traffic.
-template <typename T>
-__device__ __forceinline__ bool filter_uninitialised(const T (&x)[kXW])
-{
-    return x[6] == T(0) && x[7] == T(0) && x[8] == T(0) && x[9] == T(0);
-}
-
 // NT == 3 ("split", states larger than the Infinity Cache): the workgroups selected by `split` keep their tiles
 // cached (policy 0), all others stream (policy 2), so a fixed part of the state that fits the cache stays resident
 // from tick to tick.  split >= 0: the first `split` dispatched workgroups (spread over all XCDs by batch_block());
@@ -287,6 +335,40 @@ __device__ __forceinline__ void with_policy(int32_t split, F&& f)
         f(std::integral_constant<int, NT>{});
     }
 }
+
+// one value to an output tensor of either dtype (wave-uniform choice; the plain C++ cast of include/qle_devio.h)
+template <typename T>
+__device__ __forceinline__ void put(void* dst, int64_t k, T v, bool dst_f64)
+{
+    if (dst_f64) static_cast<double*>(dst)[k] = (double)v;
+    else static_cast<float*>(dst)[k] = (float)v;
+}
+
+// (HIP compilers only: a host compiler that reads this header for the layout arithmetic, tests/cpp/devio_index_harness.cpp, has no
+// declaration of __syncthreads.)
+#if defined(__HIPCC__)
+// The deterministic batch summary of the read-only diagnostics, second stage: one workgroup of kBlock threads adds the per-tile
+// partials [tiles][SUMS] in a fixed order.  Thread t adds field t % PITCH (< SUMS) of the tiles t / PITCH, t / PITCH + kBlock / PITCH,
+// ... in ascending order; threads 0..SUMS-1 then add the kBlock / PITCH slices in ascending order and hand the field's total to
+// out(field, total).
+template <int SUMS, int PITCH, typename Out>
+__device__ __forceinline__ void reduce_tiles(const double* __restrict__ partials, int64_t tiles, Out&& out)
+{
+    static_assert(SUMS <= PITCH && kBlock % PITCH == 0, "a slice holds every field");
+    __shared__ double part[kBlock];
+    const int f = (int)(threadIdx.x % PITCH), s = (int)(threadIdx.x / PITCH);
+    double acc = 0.0;
+    if (f < SUMS)
+        for (int64_t k = s; k < tiles; k += kBlock / PITCH) acc += partials[k * SUMS + f];
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x < SUMS) {
+        double tot = 0.0;
+        for (int k = 0; k < kBlock / PITCH; ++k) tot += part[k * PITCH + f];
+        out(f, tot);
+    }
+}
+#endif  // __HIPCC__
 
 // Dynamic LDS per wave of the fp64 kernels that keep the two top block-rows of P there (ekf_cov_home.hpp); fp32 launches with none.
 constexpr size_t kMrLdsPerWave = (size_t)kTopWords * kTile * sizeof(double);

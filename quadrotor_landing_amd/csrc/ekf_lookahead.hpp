@@ -59,7 +59,7 @@ template <typename T>
 __host__ __device__ __forceinline__ void lookahead_filter(const DevParams<T>& p, const Noise<T>& nz, T (&x)[16], T (&P)[120], const T (&u)[6],
                                                           int32_t h, const CoastLimits& lim, bool asked, int32_t& ticks)
 {
-    const bool no_state = x[6] == T(0) && x[7] == T(0) && x[8] == T(0) && x[9] == T(0);
+    const bool no_state = filter_uninitialised(x);
     x[9] = no_state ? T(1) : x[9];
     int32_t t = coast_over<T>(P, lim) ? 0 : -1;
 #pragma unroll 1

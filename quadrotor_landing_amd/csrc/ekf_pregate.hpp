@@ -16,7 +16,7 @@
 // PREDICT = false evaluates against the stored state and leaves the mask word alone: qle_innovation from device tensors.
 //
 // The predicted pose block does not depend on the accelerometer-bias rows and columns of P: of the 120 covariance words 78 are read
-// (pregate_needs below).  Only the 16-byte quad rows that hold one of them are loaded, as pose_quad does for k_innov -- which the packed
+// (pregate_needs below).  Only the 16-byte quad rows that hold one of them are loaded (load_P_rows, ekf_layout.hpp, as for k_innov) -- which the packed
 // order (ekf_device.hpp: the ab column of every block-row sits between its th and wb columns) turns into all 120 words in fp32 and 90 in
 // fp64; compact records hold nothing else than what is needed (48 / 46 words).  Words moved per filter, fp32 / fp64: full records
 // 16 + 120 / 90 + 6 + 8 in, 1 (mask) + 1 (nis) out and one byte (accepted): 152 / 122; compact records 16 + 48 / 46 + 6 + 8 in: 80 / 78.
@@ -139,22 +139,8 @@ __device__ __forceinline__ T pregate_eval(const DevParams<T>& p, const Noise<T>&
 #pragma unroll
         for (int b = a; b < 6; ++b) F[a][b] = S[a][b];
     }
-    T nis = T(0);
-    bool pd = true;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        const T d = F[c][c];
-        pd = pd && d > T(0);
-        const T inv = T(1) / d;
-#pragma unroll
-        for (int j = c + 1; j < 6; ++j) {
-            const T l = F[c][j] * inv;
-#pragma unroll
-            for (int j2 = j; j2 < 6; ++j2) F[j][j2] -= l * F[c][j2];
-            y[j] -= l * y[c];
-        }
-        nis += y[c] * y[c] * inv;
-    }
+    bool pd;
+    const T nis = ldl_solve<6, true>([&](int i, int j) -> T& { return F[i][j]; }, y, pd);
     return pd ? nis : T(NAN);
 }
 
@@ -165,100 +151,12 @@ __device__ __forceinline__ T pregate_eval(const DevParams<T>& p, const Noise<T>&
 
 namespace qle {
 
-// does quad row k (VW words) of the packed covariance hold a word pregate_eval reads?
-__host__ __device__ constexpr bool pregate_quad(int k, int vw, bool compact, bool predict)
-{
-    for (int a = 0; a < 15; ++a)
-        for (int b = a; b < 15; ++b) {
-            const bool pose = (a < 3 || (a >= 6 && a < 9)) && (b < 3 || (b >= 6 && b < 9));
-            if (!(predict ? pregate_needs(a, b) : pose)) continue;
-            const int w = p_word(a, b, compact);
-            if (w >= 0 && (w - kXW) / vw == k) return true;
-        }
-    return false;
-}
+// the covariance words pregate_eval reads: pregate_needs (PREDICT) or the pose block
+template <bool PREDICT> constexpr CovNeeds kPregateNeeds = PREDICT ? pregate_needs : pose_needs;
 // words of the covariance the kernel moves per filter (whole quad rows)
-__host__ __device__ constexpr int pregate_cov_words(int vw, bool compact, bool predict)
-{
-    int n = 0;
-    for (int k = 0; k < (compact ? kPWc : kPW) / vw; ++k) n += pregate_quad(k, vw, compact, predict) ? vw : 0;
-    return n;
-}
-static_assert(pregate_cov_words(4, false, true) == 120 && pregate_cov_words(2, false, true) == 90 && pregate_cov_words(4, true, true) == 48 &&
-              pregate_cov_words(2, true, true) == 46, "the word counts stated at the top of this file");
-
-// words [0, W) of filter i's WT-word record with plain cached loads: the IMU and tag records are read again by the tick right behind
-// (load_rec, ekf_layout.hpp, always reads them non-temporally -- right for a kernel that is their last reader)
-template <typename T, int WT, int W>
-__device__ __forceinline__ void load_rec_cached(const T* __restrict__ base, int64_t i, T (&r)[W])
-{
-    using Q = typename Quad<T>::type;
-    constexpr int VW = Quad<T>::VW;
-    const T* tb = base + wave_tile(i) * (int64_t)(WT * kTile);
-    const int lane = (int)(i & 63);
-#pragma unroll
-    for (int k = 0; k < W / VW; ++k) unpack_quad(*reinterpret_cast<const Q*>(tb + (k * kTile + lane) * VW), &r[k * VW]);
-    if constexpr (W % VW == 2) {   // fp32: the record's 8-byte tail row
-        static_assert(W == WT, "only the record's own tail may be partial");
-        const qle_f2 v = *reinterpret_cast<const qle_f2*>(tb + (W / VW) * VW * kTile + lane * 2);
-        r[W - 2] = v.x; r[W - 1] = v.y;
-    }
-}
-
-// the covariance words pregate_eval reads, from either record layout, into the 15-state register image (zero elsewhere: never read,
-// or the bias blocks a compact record does not hold)
-template <typename T, bool COMPACT, bool PREDICT, int... K>
-__device__ __forceinline__ void load_pregate_quads(const T* __restrict__ tb, int lane, T (&w)[kPW], std::integer_sequence<int, K...>)
-{
-    using Q = typename Quad<T>::type;
-    constexpr int VW = Quad<T>::VW;
-    (..., [&] {
-        if constexpr (pregate_quad(K, VW, COMPACT, PREDICT)) unpack_quad(*reinterpret_cast<const Q*>(tb + ((kXW / VW + K) * kTile + lane) * VW), &w[K * VW]);
-    }());
-}
-// per slot of the register image: the loaded covariance word it takes, or -1 (zero).  A compile-time table: written as a plain loop
-// over pregate_quad in the kernel, the selection is not folded and runs on the scalar unit (some 20 000 SALU instructions per wave).
-template <int VW, bool COMPACT, bool PREDICT>
-struct PregateSrc {
-    int w[kPW];
-    constexpr PregateSrc() : w{}
-    {
-        bool quad[kPW / VW] = {};
-        for (int k = 0; k < (COMPACT ? kPWc : kPW) / VW; ++k) quad[k] = pregate_quad(k, VW, COMPACT, PREDICT);
-        for (int a = 0; a < 15; ++a)
-            for (int b = a; b < 15; ++b) {
-                const int rw = p_word(a, b, COMPACT);
-                w[sidx(a, b)] = (rw >= 0 && quad[(rw - kXW) / VW]) ? rw - kXW : -1;
-            }
-    }
-};
-template <typename T, bool COMPACT, bool PREDICT, int... K>
-__device__ __forceinline__ void place_pregate_words(const T (&w)[kPW], T (&P)[kPW], std::integer_sequence<int, K...>)
-{
-    constexpr PregateSrc<Quad<T>::VW, COMPACT, PREDICT> src{};
-    (..., [&] {
-        if constexpr (src.w[K] >= 0) P[K] = w[src.w[K]];
-        else P[K] = T(0);
-    }());
-}
-template <typename T, bool COMPACT, bool PREDICT>
-__device__ __forceinline__ void load_P_pregate(const T* __restrict__ st, int64_t i, T (&P)[kPW])
-{
-    constexpr int VW = Quad<T>::VW;
-    const T* tb = st + wave_tile(i) * (int64_t)(kSW * kTile);
-    const int lane = (int)(i & 63);
-    T w[kPW];
-    load_pregate_quads<T, COMPACT, PREDICT>(tb, lane, w, std::make_integer_sequence<int, (COMPACT ? kPWc : kPW) / VW>{});
-    place_pregate_words<T, COMPACT, PREDICT>(w, P, std::make_integer_sequence<int, kPW>{});
-}
-
-// one value to an output tensor of either dtype (wave-uniform choice; the plain C++ cast of include/qle_devio.h)
-template <typename T>
-__device__ __forceinline__ void put(void* dst, int64_t k, T v, bool dst_f64)
-{
-    if (dst_f64) static_cast<double*>(dst)[k] = (double)v;
-    else static_cast<float*>(dst)[k] = (float)v;
-}
+template <int VW, bool COMPACT, bool PREDICT> constexpr int pregate_cov_words = CovSrc<VW, COMPACT, kPregateNeeds<PREDICT>>{}.words;
+static_assert(pregate_cov_words<4, false, true> == 120 && pregate_cov_words<2, false, true> == 90 && pregate_cov_words<4, true, true> == 48 &&
+              pregate_cov_words<2, true, true> == 46, "the word counts stated at the top of this file");
 
 // One lane per filter, one wave per workgroup (a workgroup is one 64-filter tile).  Reads the state, never writes it.
 // zs: the tag records (z 7 words + mask word); PREDICT stores the mask word back, kept where accepted and cleared elsewhere.
@@ -272,14 +170,16 @@ __global__ __launch_bounds__(kTile, 2) void k_pregate(const T* __restrict__ st, 
     args_early(st, us, zs, B);
     const int64_t i = (int64_t)blockIdx.x * kTile + threadIdx.x;   // the records are allocated for whole tiles: every lane may load
     T x[kXW], P[kPW], u[kUW], zr[kZW];
-    load_rec_cached<T, kZW, kZW>(zs, i, zr);
-    if constexpr (PREDICT) load_rec_cached<T, kUW, kUW>(us, i, u);
+    // cached loads: the IMU and tag records are read again by the tick right behind (load_rec reads them non-temporally by default --
+    // right for a kernel that is their last reader)
+    load_rec<T, kZW, 0, kZW, kCached>(zs, i, zr);
+    if constexpr (PREDICT) load_rec<T, kUW, 0, kUW, kCached>(us, i, u);
     else {
 #pragma unroll
         for (int k = 0; k < kUW; ++k) u[k] = T(0);
     }
-    load_rec_cached<T, kSW, kXW>(st, i, x);
-    load_P_pregate<T, COMPACT, PREDICT>(st, i, P);
+    load_rec<T, kSW, 0, kXW>(st, i, x);
+    load_P_rows<T, COMPACT, kPregateNeeds<PREDICT>>(st, i, P);
     Noise<T> nz;
     load_noise<T, PFP>(p, pfp, i, nz);
     const bool dead = filter_uninitialised(x);

@@ -6,8 +6,8 @@ is made before any GPU call (without a GPU a HIP call would fail with another er
 
 What the host build covers: the arithmetic of pregate_eval and the set of covariance words it reads (tests/cpp/pregate_harness.cpp fills
 every word outside pregate_needs with NaN).  What it does not cover: the kernel's own loads -- which 16-byte quads it fetches
-(pregate_quad, load_P_pregate) and the record loads (load_rec_cached).  Those run only on the GPU and are held by tests/test_gpu_gate.py;
-here only their word counts are checked, by the static_asserts of ekf_pregate.hpp at compile time.
+(load_P_rows of ekf_layout.hpp over pregate_needs or the pose block) and the record loads (load_rec).  Those run only on the GPU and are
+held by tests/test_gpu_gate.py; here only their word counts are checked, by the static_asserts of ekf_pregate.hpp at compile time.
 
 Measured deviations of the host-compiled arithmetic from the reference (worst over the grid, B = 300, innovations up to 170 degrees;
 bars in gate_util.TOL):
