@@ -163,6 +163,31 @@ __device__ __forceinline__ void store_row(T* __restrict__ tb, int lane, int k, c
     *reinterpret_cast<Q*>(tb + tile_word<T>(k * Vec<T>::V, lane, WT)) = qle::pack_quad(r);
 }
 
+// The record stores of a pack, one definition for k_dv_pack and the many-tick pack of sequence_kernels.hpp.
+// A lane's six IMU words -> its IMU record in the tile at tu: the quad rows, and for fp32 the record's 8-byte tail row.
+template <typename T>
+__device__ __forceinline__ void store_imu_record(T* __restrict__ tu, int lane, const T* r)
+{
+    constexpr int V = Vec<T>::V;
+#pragma unroll
+    for (int k = 0; k < kUW / V; ++k) store_row<T, kUW>(tu, lane, k, &r[k * V]);
+    if constexpr (kUW % V != 0) {   // fp32: the record's 8-byte tail row
+        qle::qle_f2 t = {(float)r[4], (float)r[5]};
+        *reinterpret_cast<qle::qle_f2*>(reinterpret_cast<float*>(tu) + tile_word<float>(4, lane, kUW)) = t;
+    }
+}
+// The mask word of filter i, made in registers: mask == nullptr means all set (k_pack_z_off's meaning).
+template <typename T>
+__device__ __forceinline__ T mask_word(const uint8_t* __restrict__ mask, int64_t i) { return (mask == nullptr || mask[i]) ? T(1) : T(0); }
+// A lane's eight tag words (z 7 + mask word) -> its tag record in the tile at tz.
+template <typename T>
+__device__ __forceinline__ void store_tag_record(T* __restrict__ tz, int lane, const T* r)
+{
+    constexpr int V = Vec<T>::V;
+#pragma unroll
+    for (int k = 0; k < kZW / V; ++k) store_row<T, kZW>(tz, lane, k, &r[k * V]);
+}
+
 // ------------------------------------------------------------------ kernels
 // u [B][6] (+ z [B][7], mask [B]) of S -> the tick's IMU record (+ tag record) of T.  zd == nullptr: no tag record; z == nullptr: identity
 // pose; mask == nullptr: all set (k_pack_z_off's meaning).
@@ -172,7 +197,6 @@ __global__ void __launch_bounds__(kTile) k_dv_pack(const S* __restrict__ u, cons
 {
     __shared__ T lu[kTile * kPitchU];
     __shared__ T lz[kTile * kPitchZ];
-    constexpr int V = Vec<T>::V;
     const int lane = (int)threadIdx.x;
     const int64_t tile = blockIdx.x;
     const int nv = tile_valid(B, tile);
@@ -183,20 +207,12 @@ __global__ void __launch_bounds__(kTile) k_dv_pack(const S* __restrict__ u, cons
     T r[8];
 #pragma unroll
     for (int w = 0; w < kUW; ++w) r[w] = lu[lds_word(lane, w, kPitchU)];
-    T* tu = ud + tile_base(tile, kUW);
-#pragma unroll
-    for (int k = 0; k < kUW / V; ++k) store_row<T, kUW>(tu, lane, k, &r[k * V]);
-    if constexpr (kUW % V != 0) {   // fp32: the record's 8-byte tail row
-        qle::qle_f2 t = {(float)r[4], (float)r[5]};
-        *reinterpret_cast<qle::qle_f2*>(reinterpret_cast<float*>(tu) + tile_word<float>(4, lane, kUW)) = t;
-    }
+    store_imu_record<T>(ud + tile_base(tile, kUW), lane, r);
     if (!zd) return;
 #pragma unroll
     for (int w = 0; w < 7; ++w) r[w] = z ? lz[lds_word(lane, w, kPitchZ)] : (w == 6 ? T(1) : T(0));
-    r[7] = (mask == nullptr || mask[tile * kTile + lane]) ? T(1) : T(0);
-    T* tz = zd + tile_base(tile, kZW);
-#pragma unroll
-    for (int k = 0; k < kZW / V; ++k) store_row<T, kZW>(tz, lane, k, &r[k * V]);
+    r[7] = mask_word<T>(mask, tile * kTile + lane);
+    store_tag_record<T>(zd + tile_base(tile, kZW), lane, r);
 }
 
 // state records of T -> x [B][16], P [B][N][N] of D (either may be null).  N = 15 or 9; compact only with N = 9.

@@ -26,6 +26,10 @@ Look-ahead (lookahead.py, libqle_lookahead.so): `lookahead(u, h)` returns a `For
 IMU sample held, computed in one read-only launch into a workspace of its own and readable through the same calls (`state`, `report`,
 `health`, `nees`, `lookahead` again), with the coast budget `ticks_to_limit` when a sigma limit is given.
 
+A whole tensor sequence per call (sequence.py, libqle_sequence.so): `sequence(u_seq, z_seq, meas_ticks, mask_seq)` packs K ticks of
+tensors into a `DeviceSequence` with ceil(K / 32) launches, and `run(seq, ...)` runs them from one C loop -- with the gate, a report
+trace and a NEES trace every so many ticks where asked -- instead of K Python calls of `tick`; the bits are those of the `tick` loop.
+
 Still host-fed through `BatchedRelativePoseEKF`: `set_state` and the per-filter stamps of `dynamic_meas_delay`
 (`filter_update(t_curr=..., apriltag_time=...)`).
 """
@@ -38,6 +42,7 @@ from . import consistency as _cons
 from . import gate as _gate
 from . import health as _health
 from . import lookahead as _look
+from . import sequence as _seqm
 from ._lib import QLE_ERR_STATE, QLE_F32, QleDeviceView, QleInputsView, QleError, check, lib, load_side_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -355,6 +360,131 @@ class DeviceIO:
             self._seed_from_slot(D, view, iv, zero_u, z, reseeded, src, reinit_bias)
         return status, reseeded
 
+    # ---- a whole tensor sequence per call
+    def _check_sequence(self, u_seq, z_seq, mask_seq, n_ticks, meas_ticks, t0):
+        """The argument checks of `sequence` / `DeviceSequence.pack` (before any GPU call).  Returns (source dtype name, n).
+        n_ticks None: the sequence is as long as u_seq."""
+        B = self.ekf.batch
+        shape = tuple(getattr(u_seq, "shape", ()))
+        if len(shape) != 3 or shape[0] < 1:
+            raise ValueError(f"u_seq: expected shape (K, {B}, 6) with K >= 1, got {shape}")
+        n = int(shape[0])
+        src = self._check(u_seq, "u_seq", (n, B, 6), _FLOATS)
+        if n_ticks is None:
+            n_ticks = n
+        t0 = int(t0)
+        if t0 < 0 or t0 + n > n_ticks:
+            raise ValueError(f"ticks [{t0}, {t0 + n}) reach beyond the sequence of {n_ticks} ticks")
+        ticks = _seqm.check_meas_ticks(meas_ticks, n_ticks)
+        m = sum(1 for t in ticks if t0 <= t < t0 + n)
+        if z_seq is None:
+            if mask_seq is not None:
+                raise ValueError("mask_seq given without z_seq")
+            if m > 0:
+                raise ValueError(f"{m} ticks of the range have a tag slot (meas_ticks) but z_seq is None")
+        else:
+            if m == 0:
+                raise ValueError("z_seq given but no tick of the range has a tag slot (meas_ticks)")
+            if self._check(z_seq, "z_seq", (m, B, 7), _FLOATS) != src:
+                raise ValueError("u_seq and z_seq must have the same dtype")
+            if mask_seq is not None:
+                self._check_mask(mask_seq, B, "mask_seq", (m, B))
+                if mask_seq.data_ptr() % 16 != 0:
+                    raise ValueError("mask_seq: tensor storage must be 16-byte aligned")
+        return src, n
+
+    def sequence(self, u_seq, z_seq=None, meas_ticks=None, mask_seq=None):
+        """K ticks of tensors -> a `sequence.DeviceSequence`: u_seq [K,B,6]; meas_ticks, a host list of the M strictly increasing tick
+        indices in [0, K) that carry a tag pose; z_seq [M,B,7] and mask_seq [M,B] (uint8 / bool; None = all) for those ticks, in tick
+        order (float32 or float64, u_seq and z_seq alike).  Creates the K-tick sequence and packs it with ONE call (ceil(K / 32)
+        launches of k_sq_pack instead of K packs).  Asynchronous; the tensors may be reused as soon as the call returns."""
+        src, n = self._check_sequence(u_seq, z_seq, mask_seq, None, meas_ticks, 0)
+        seq = _seqm.DeviceSequence(self, n, _seqm.check_meas_ticks(meas_ticks, n))
+        try:
+            return seq.pack(u_seq, z_seq, mask_seq)
+        except Exception:
+            seq.close()
+            raise
+
+    def run(self, seq, t0=0, n=None, chi2_max=None, return_nis=False, trace_every=None, trace=("report",), x_true_seq=None, blocks="all",
+            chi2_hi=float("inf"), dtype=None):
+        """Ticks [t0, t0 + n) of a `DeviceSequence` (n None: to its end) in ONE native call: what n calls of `tick` do, in the same
+        order, from a C loop (include/qle_sequence.h), and bit for bit their results.  Works on whatever `tick` works on.
+
+        chi2_max: the chi-square gate of `tick` in front of every tick that has a tag slot; the result then has `accepted` [m,B]
+        (uint8), one slice per tag tick of the range in tick order, and with return_nis=True `nis` [m,B].  Refused with multirate_ekf.
+        A gated run leaves the accepted masks in the sequence: running it again without a gate replays the accepted corrections.
+        trace_every = e: after every e-th tick of the range the kinds named in `trace` are taken -- "report": the dict of `report()` as
+        [J,B,...] tensors; "nees": `nees(x_true_seq[j], blocks=..., chi2_hi=...)` as nees [J,B] and summary [J,8], against
+        x_true_seq [J,B,16] -- J = n // e slices, slice j after tick t0 + (j + 1) e - 1.  dtype: of nis, report and nees (None: the
+        handle's).  Returns a `sequence.SequenceResult` of device tensors; asynchronous, no synchronisation."""
+        B = self.ekf.batch
+        if not isinstance(seq, _seqm.DeviceSequence) or seq.io.ekf is not self.ekf or seq.inputs is None:
+            raise ValueError("seq: expected an open DeviceSequence made by this handle's DeviceIO.sequence")
+        t0 = int(t0)
+        n = seq.n_ticks - t0 if n is None else int(n)
+        if t0 < 0 or n < 0 or t0 + n > seq.n_ticks:
+            raise ValueError(f"ticks [{t0}, {t0 + n}) reach beyond the sequence of {seq.n_ticks} ticks")
+        if chi2_max is None:
+            if return_nis:
+                raise ValueError("return_nis given without chi2_max")
+        else:
+            chi2_max = float(chi2_max)
+            if not chi2_max > 0.0:
+                raise ValueError(f"chi2_max must be > 0 (got {chi2_max})")
+            self._refuse_multirate()
+        kinds = (trace,) if isinstance(trace, str) else tuple(trace)
+        if set(kinds) - set(_seqm.TRACE_KINDS) or not kinds:
+            raise ValueError(f"trace: expected kinds out of {_seqm.TRACE_KINDS}, got {kinds}")
+        if trace_every is None:
+            if kinds != ("report",) or x_true_seq is not None:
+                raise ValueError("trace kinds or x_true_seq given without trace_every")
+            kinds, J = (), 0
+        else:
+            if int(trace_every) != trace_every or int(trace_every) < 1:
+                raise ValueError(f"trace_every must be an integer >= 1 (got {trace_every})")
+            trace_every = int(trace_every)
+            J = n // trace_every
+        dn = self._out_dtype(dtype)
+        opts = _seqm.QsqRunOpts()
+        opts.struct_size = C.sizeof(opts)
+        opts.dst_dtype = _FLOATS[dn]
+        opts.trace_every = trace_every or 0
+        if "nees" in kinds:
+            if x_true_seq is None:
+                raise ValueError('trace "nees" needs x_true_seq')
+            opts.true_dtype = _FLOATS[self._check(x_true_seq, "x_true_seq", (J, B, 16), _FLOATS)]
+            opts.blocks = _cons.block_mask(blocks, self.ekf.num_states)
+            opts.chi2_hi = _cons.check_chi2_hi(chi2_hi)
+        elif x_true_seq is not None:
+            raise ValueError('x_true_seq given without "nees" in trace')
+        S, D = _seqm.sequence_lib(), devio_lib()
+        opts.params = C.pointer(self.ekf.params)
+        view = self._view()
+        Bp = int(view.padded_batch)
+        res = _seqm.SequenceResult()
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
+        if chi2_max is not None:
+            opts.chi2_max = chi2_max
+            m = seq.slots(t0, n)
+            acc = self._alloc([(m, Bp)], "uint8")[0]
+            nis = self._alloc([(m, Bp)], dn)[0] if return_nis else None
+            opts.accepted, opts.nis = ptr(acc), ptr(nis)
+            res.accepted, res.nis = acc[:, :B], None if nis is None else nis[:, :B]
+        if "report" in kinds:
+            bufs = self._alloc([(J, Bp) + s for _, s in self._REPORT], dn)
+            opts.pose, opts.pose_cov, opts.vel, opts.bias = (ptr(b) for b in bufs)
+            res.report = {k: b[:, :B] for (k, _), b in zip(self._REPORT, bufs)}
+        if "nees" in kinds:
+            nees, summary = self._alloc([(J, Bp)], dn)[0], self._alloc([(J, 8)], "float64")[0]
+            opts.x_true_seq, opts.nees, opts.summary = ptr(x_true_seq), ptr(nees), ptr(summary)
+            res.nees, res.summary = nees[:, :B], summary
+            if J == 0:
+                opts.true_dtype, opts.blocks, opts.chi2_hi = 0, 0, 0.0
+        with self._ordered(D, view, x_true_seq):
+            _seqm.scheck(S.qsq_run(self.ekf._h, seq.inputs._h, t0, n, C.byref(opts)))
+        return res
+
     # ---- look-ahead: state and covariance h ticks ahead, read-only
     def lookahead(self, u, h, mask=None, sigma_r_max=float("inf"), sigma_theta_max=float("inf")):
         """The forecast h ticks ahead (0 <= h <= lookahead.MAX_HORIZON) with the IMU sample u [B,6] (float32 or float64) held: what h
@@ -383,19 +513,20 @@ class DeviceIO:
                                          None if coast is None else C.byref(coast), None if ticks is None else ticks.data_ptr()))
         return _look.Forecast(self, ahead, workspace, h, ticks)
 
-    def _check_mask(self, mask, B):
+    def _check_mask(self, mask, B, name="mask", shape=None):
+        shape = (B,) if shape is None else tuple(shape)
         for attr in ("data_ptr", "dtype", "shape", "device"):
             if not hasattr(mask, attr):
-                raise ValueError(f"mask: expected a device tensor, got {type(mask).__name__}")
+                raise ValueError(f"{name}: expected a device tensor, got {type(mask).__name__}")
         kind, idx = _device_index(mask)
         if kind not in ("cuda", "hip") or idx != self.ekf.device:
-            raise ValueError(f"mask: tensor is on {mask.device}, the filter handle is on GPU {self.ekf.device}")
+            raise ValueError(f"{name}: tensor is on {mask.device}, the filter handle is on GPU {self.ekf.device}")
         if _dtype_name(mask) not in _MASKS:
-            raise ValueError(f"mask: dtype {mask.dtype} not supported, expected uint8 or bool")
-        if tuple(mask.shape) != (B,):
-            raise ValueError(f"mask: expected shape {(B,)}, got {tuple(mask.shape)}")
+            raise ValueError(f"{name}: dtype {mask.dtype} not supported, expected uint8 or bool")
+        if tuple(mask.shape) != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(mask.shape)}")
         if hasattr(mask, "is_contiguous") and not mask.is_contiguous():
-            raise ValueError("mask: tensor must be contiguous")
+            raise ValueError(f"{name}: tensor must be contiguous")
 
     # ---- outputs as device tensors
     def _out_dtype(self, dtype):
