@@ -9,5 +9,6 @@ from . import replay  # noqa: F401
 from . import consistency  # noqa: F401
 from . import health  # noqa: F401
 from . import lookahead  # noqa: F401
+from . import score  # noqa: F401
 from . import sequence  # noqa: F401
 from .sequence import DeviceSequence, SequenceResult  # noqa: F401

@@ -120,14 +120,6 @@ __device__ __forceinline__ void load_truth(const void* __restrict__ xt, int64_t 
     }
 }
 
-// the same value in every lane, by a fixed tree: deterministic
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // One lane per filter, one wave per workgroup (a workgroup is one 64-filter tile).  Reads the state, never writes it.
 // xt [B][16] of float32 / float64 (true_f64), mask [B] or null; nees [B], err [B][n_err] of dst dtype and partials [tiles][8] (fp64):
 // any may be null (wave-uniform).  fp64 holds 240 registers of P: one wave per SIMD, as k_predict<double>; fp32 fits two.

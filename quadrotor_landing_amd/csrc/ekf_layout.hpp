@@ -347,7 +347,16 @@ __device__ __forceinline__ void put(void* dst, int64_t k, T v, bool dst_f64)
 // (HIP compilers only: a host compiler that reads this header for the layout arithmetic, tests/cpp/devio_index_harness.cpp, has no
 // declaration of __syncthreads.)
 #if defined(__HIPCC__)
-// The deterministic batch summary of the read-only diagnostics, second stage: one workgroup of kBlock threads adds the per-tile
+// The deterministic batch summary of the read-only diagnostics, first stage: a wave's sum by xor-shuffles -- the same value in every
+// lane, by a fixed tree (k_nees, ekf_consistency.hpp; k_score_tiles, ekf_score.hpp).
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// Second stage: one workgroup of kBlock threads adds the per-tile
 // partials [tiles][SUMS] in a fixed order.  Thread t adds field t % PITCH (< SUMS) of the tiles t / PITCH, t / PITCH + kBlock / PITCH,
 // ... in ascending order; threads 0..SUMS-1 then add the kBlock / PITCH slices in ascending order and hand the field's total to
 // out(field, total).

@@ -90,10 +90,12 @@ __host__ __device__ __forceinline__ void innovation_cov(const quad::FactorIn<T>&
 // nu = dy (EKF.cpp:447-450), S = G P G^T + R_k (EKF.cpp:475; symmetric, both triangles filled) and the returned NIS = dy^T S^-1 dy of
 // tag pose z.  PREDICT: against the state one prediction_step (EKF.cpp:346-415) with IMU sample u ahead of (x, Po); x is advanced in
 // place.  Otherwise against (x, Po) as they are, and u is not read.  Of Po only the words pregate_needs names are read (PREDICT) or the
-// pose block (otherwise).  NIS is NaN where S is not positive definite.
+// pose block (otherwise).  pregate_eval_pivots also hands back the pivots d_m of S = L D L^T (log det S = sum log d_m: k_score,
+// ekf_score.hpp) and pd, whether every one of them is > 0; it returns the quadratic form as the factor left it.  pregate_eval is that
+// with NaN where S is not positive definite.
 template <typename T, bool DIRECT, bool PREDICT>
-__device__ __forceinline__ T pregate_eval(const DevParams<T>& p, const Noise<T>& nzl, T (&x)[16], const T (&Po)[120], const T (&u)[6],
-                                          const T (&z)[7], T (&nu)[6], T (&S)[6][6])
+__device__ __forceinline__ T pregate_eval_pivots(const DevParams<T>& p, const Noise<T>& nzl, T (&x)[16], const T (&Po)[120], const T (&u)[6],
+                                                 const T (&z)[7], T (&nu)[6], T (&S)[6][6], T (&d)[6], bool& pd)
 {
     using SQ = quad::ScalarQ<T>;
     quad::FactorIn<T> in;
@@ -139,8 +141,19 @@ __device__ __forceinline__ T pregate_eval(const DevParams<T>& p, const Noise<T>&
 #pragma unroll
         for (int b = a; b < 6; ++b) F[a][b] = S[a][b];
     }
-    bool pd;
     const T nis = ldl_solve<6, true>([&](int i, int j) -> T& { return F[i][j]; }, y, pd);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) d[a] = F[a][a];
+    return nis;
+}
+
+template <typename T, bool DIRECT, bool PREDICT>
+__device__ __forceinline__ T pregate_eval(const DevParams<T>& p, const Noise<T>& nzl, T (&x)[16], const T (&Po)[120], const T (&u)[6],
+                                          const T (&z)[7], T (&nu)[6], T (&S)[6][6])
+{
+    T d[6];
+    bool pd;
+    const T nis = pregate_eval_pivots<T, DIRECT, PREDICT>(p, nzl, x, Po, u, z, nu, S, d, pd);
     return pd ? nis : T(NAN);
 }
 

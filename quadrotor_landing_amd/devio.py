@@ -30,6 +30,10 @@ A whole tensor sequence per call (sequence.py, libqle_sequence.so): `sequence(u_
 tensors into a `DeviceSequence` with ceil(K / 32) launches, and `run(seq, ...)` runs them from one C loop -- with the gate, a report
 trace and a NEES trace every so many ticks where asked -- instead of K Python calls of `tick`; the bits are those of the `tick` loop.
 
+Innovation scoring for noise sweeps (score.py, libqle_score.so): `scorer()` returns a `Scorer` whose `observe(u, z, mask)` in front of a
+`tick`, or `run(seq)` in place of `run`, accumulates every filter's innovation log-likelihood and per-component consistency statistics
+on the GPU -- one read-only launch per tag tick, the ticks themselves unchanged.
+
 Still host-fed through `BatchedRelativePoseEKF`: `set_state` and the per-filter stamps of `dynamic_meas_delay`
 (`filter_update(t_curr=..., apriltag_time=...)`).
 """
@@ -42,6 +46,7 @@ from . import consistency as _cons
 from . import gate as _gate
 from . import health as _health
 from . import lookahead as _look
+from . import score as _score
 from . import sequence as _seqm
 from ._lib import QLE_ERR_STATE, QLE_F32, QleDeviceView, QleInputsView, QleError, check, lib, load_side_library
 
@@ -484,6 +489,14 @@ class DeviceIO:
         with self._ordered(D, view, x_true_seq):
             _seqm.scheck(S.qsq_run(self.ekf._h, seq.inputs._h, t0, n, C.byref(opts)))
         return res
+
+    # ---- innovation scoring for noise sweeps
+    def scorer(self):
+        """A `score.Scorer` for this handle: it owns zeroed fp64 accumulators on the GPU, `observe(u, z, mask)` in front of a `tick` or
+        `run(seq)` in place of `run` adds every tag tick's innovation to them (one read-only launch per tag tick, k_score), and
+        `result()` / `summary()` read them as per-filter log-likelihood and innovation consistency statistics.  Refused with
+        multirate_ekf."""
+        return _score.Scorer(self)
 
     # ---- look-ahead: state and covariance h ticks ahead, read-only
     def lookahead(self, u, h, mask=None, sigma_r_max=float("inf"), sigma_theta_max=float("inf")):

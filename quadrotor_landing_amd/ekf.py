@@ -343,6 +343,19 @@ class BatchedRelativePoseEKF:
         xt[:, 0:3] = pose[:, 0:3]; xt[:, 6:10] = pose[:, 3:7]; xt[:, 10:16] = bias + static
         return self.nees(xt, blocks="r+theta+ab+wb" if self.num_states == 15 else "r+theta", chi2_hi=chi2_hi)
 
+    # ---- innovation scoring for noise sweeps (include/qle_score.h)
+    def score(self, inputs, t0, n):
+        """Ticks [t0, t0 + n) of `inputs`, scored: what `run(inputs, t0, n)` does, with every tag pose's innovation against the
+        predicted state accumulated per filter on the device (k_score, read-only, in front of the unchanged tick).  Returns a dict of
+        numpy arrays: acc [40,B] (the accumulator words of include/qle_score.h) and the fields of `score.Score` -- n, n_bad, nis_mean,
+        loglik [B], var_ratio, rho1, nu_mean [B,6].  Refused with multirate_ekf."""
+        from . import score as sc
+        acc = sc.run_host(self, inputs, t0, n)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            s = sc.Score(acc)
+        return {"acc": acc, "n": s.n, "n_bad": s.n_bad, "nis_mean": s.nis_mean, "loglik": s.loglik, "var_ratio": s.var_ratio, "rho1": s.rho1,
+                "nu_mean": s.nu_mean}
+
     # ---- filter health
     def health(self, mask=None, sigma_r_max=float("inf"), sigma_v_max=float("inf"), sigma_theta_max=float("inf"), qnorm_tol=1e-3, select=None):
         """Which filters are broken?  Host arrays in and out; the classification runs on the device (k_health), the state is unchanged.

@@ -1,0 +1,156 @@
+"""ctypes binding of include/qle_score.h (libqle_score.so): innovation scoring for noise sweeps.
+
+Which per-filter parameter set of a Monte-Carlo sweep is better?  Without a truth: the innovation log-likelihood of every filter over
+the run, log L = -1/2 sum (NIS + log det S + 6 ln 2 pi), and per-component consistency statistics of the innovation.  One read-only
+kernel per tag tick (k_score, csrc/ekf_score.hpp: the arithmetic of the gate's k_pregate with an fp64 accumulator record per filter)
+in front of the unchanged tick; it never writes the mask word, so a scored run is the plain run.  `DeviceIO.scorer()` (devio.py) makes
+a `Scorer` for device tensors, `BatchedRelativePoseEKF.score` (ekf.py) is the host-array form.  There is no fallback: a missing library
+is an error.
+"""
+import ctypes as C
+import math
+import os
+
+from ._lib import QLE_ERR_STATE, QleDeviceView, QleError, QleInputsView, QleParams, load_side_library
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+SCORE_LIB_PATH = os.environ.get("QLE_SCORE_LIB") or os.path.join(_HERE, "libqle_score.so")
+
+WORDS, SUMS = 40, 30   # QSC_WORDS, QSC_SUMS
+# the words of an accumulator record: name -> (first word, count)
+LAYOUT = {"n": (0, 1), "sum_nis": (1, 1), "sum_nis_sq": (2, 1), "sum_logdet": (3, 1), "n_bad": (4, 1), "n_pairs": (5, 1), "sum_nu": (6, 6),
+          "sum_nu_sq": (12, 6), "sum_S_diag": (18, 6), "sum_lag": (24, 6), "nu_prev": (30, 6)}
+LN_2PI = math.log(2.0 * math.pi)
+
+_vp = C.c_void_p
+_pview, _pin, _ppar = C.POINTER(QleDeviceView), C.POINTER(QleInputsView), C.POINTER(QleParams)
+# every symbol include/qle_score.h declares: name -> (restype, argtypes)
+SYMBOLS = {
+    "qsc_last_error": (C.c_char_p, []),
+    "qsc_launch_count": (C.c_int64, []),
+    "qsc_score_tick": (C.c_int, [_pview, _pin, _ppar, _vp]),
+    "qsc_run": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _ppar, _vp]),
+    "qsc_summary": (C.c_int, [_pview, _vp, _vp, _vp]),
+    "qsc_run_host": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _ppar, C.POINTER(C.c_double)]),
+}
+
+_qlib = None
+
+
+def score_lib():
+    """Load libqle_score.so; raises (never falls back) when it is missing."""
+    global _qlib
+    if _qlib is None:
+        _qlib = load_side_library(SCORE_LIB_PATH, SYMBOLS, "innovation scoring", needs_tick_library=True)
+    return _qlib
+
+
+def qcheck(rc):
+    if rc != 0:
+        raise QleError(rc, score_lib().qsc_last_error().decode())
+
+
+def refuse_multirate(params):
+    if params.multirate_ekf:
+        raise QleError(QLE_ERR_STATE, "scoring does not support multirate_ekf: a delayed measurement's innovation belongs to a history entry")
+
+
+class Score:
+    """The accumulators of a `Scorer` read as statistics, per filter (torch tensors on the device, or numpy arrays from
+    `BatchedRelativePoseEKF.score`): n and n_bad [B] (scored innovations; ticks the filter was on but its NIS was not finite),
+    nis_mean [B] (6 for a consistent filter), loglik [B] = -1/2 (sum NIS + sum log det S + 6 n ln 2 pi), var_ratio [B,6] = sum nu_k^2 /
+    sum S_kk (1 for a consistent filter; the components are those of R_r and R_ang), rho1 [B,6] = sum nu_k nu_k^- / sum nu_k^2 (the
+    whiteness test, 0 for a consistent filter) and nu_mean [B,6].  A filter that was never scored has NaN ratios and loglik 0."""
+
+    def __init__(self, acc):
+        """acc: [WORDS, B] float64, a torch tensor or a numpy array."""
+        w = lambda name: acc[LAYOUT[name][0]:LAYOUT[name][0] + LAYOUT[name][1]]   # noqa: E731
+        n = acc[0]
+        self.n, self.n_bad, self.n_pairs = n, acc[4], acc[5]
+        self.nis_mean = acc[1] / n
+        self.loglik = -0.5 * (acc[1] + acc[3] + 6.0 * LN_2PI * n)
+        self.var_ratio = (w("sum_nu_sq") / w("sum_S_diag")).T
+        self.rho1 = (w("sum_lag") / w("sum_nu_sq")).T
+        self.nu_mean = (w("sum_nu") / n).T
+
+
+class Scorer:
+    """Innovation scoring of a handle fed from device tensors (`DeviceIO.scorer()`).  Owns a zeroed accumulator tensor `acc`
+    [WORDS, padded batch] (float64, include/qle_score.h) on the handle's GPU.  Every call is asynchronous and none synchronises."""
+
+    def __init__(self, io):
+        import torch
+        refuse_multirate(io.ekf.params)
+        self.io = io
+        self._Bp = -(-io.ekf.batch // 64) * 64
+        self.acc = torch.zeros((WORDS, self._Bp), dtype=torch.float64, device=torch.device("cuda", io.ekf.device))
+
+    def reset(self):
+        self.acc.zero_()
+
+    def observe(self, u, z, mask=None):
+        """Score the tag poses of the tick `io.tick(u, z, mask)` is about to run -- call it BEFORE that tick: packs u [B,6], z [B,7] and
+        mask [B] (uint8 / bool; None = all) into the slot the tick will pack again, and adds every filter's innovation against the
+        predicted state to its accumulators.  One pack and ONE launch of k_score; the state is not touched."""
+        from . import devio as _devio
+        io = self.io
+        B = io.ekf.batch
+        src = io._check(u, "u", (B, 6), _devio._FLOATS)
+        if io._check(z, "z", (B, 7), _devio._FLOATS) != src:
+            raise ValueError("u and z must have the same dtype")
+        if mask is not None:
+            io._check_mask(mask, B)
+        refuse_multirate(io.ekf.params)
+        D, Q = _devio.devio_lib(), score_lib()
+        view = io._view()
+        iv = io._inputs_view(1)
+        with io._ordered(D, view, u, z, mask, self.acc):
+            _devio._dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), u.data_ptr(), z.data_ptr(), None if mask is None else mask.data_ptr(),
+                                             _devio._FLOATS[src]))
+            qcheck(Q.qsc_score_tick(C.byref(view), C.byref(iv), C.byref(io.ekf.params), self.acc.data_ptr()))
+
+    def run(self, seq, t0=0, n=None):
+        """Ticks [t0, t0 + n) of a `DeviceSequence` (n None: to its end), scored, in ONE native call (qsc_run): what `io.run(seq, t0, n)`
+        does -- state and sequence end with its bits -- with k_score in front of every tick that has a tag slot."""
+        from . import devio as _devio
+        from . import sequence as _seqm
+        io = self.io
+        if not isinstance(seq, _seqm.DeviceSequence) or seq.io.ekf is not io.ekf or seq.inputs is None:
+            raise ValueError("seq: expected an open DeviceSequence made by this handle's DeviceIO.sequence")
+        t0 = int(t0)
+        n = seq.n_ticks - t0 if n is None else int(n)
+        if t0 < 0 or n < 0 or t0 + n > seq.n_ticks:
+            raise ValueError(f"ticks [{t0}, {t0 + n}) reach beyond the sequence of {seq.n_ticks} ticks")
+        refuse_multirate(io.ekf.params)
+        D, Q = _devio.devio_lib(), score_lib()
+        view = io._view()
+        with io._ordered(D, view, self.acc):
+            qcheck(Q.qsc_run(io.ekf._h, seq.inputs._h, t0, n, C.byref(io.ekf.params), self.acc.data_ptr()))
+
+    def result(self):
+        """The accumulators as a `Score` of device tensors [B] / [B,6]; no synchronisation."""
+        return Score(self.acc[:, :self.io.ekf.batch])
+
+    def summary(self, mask=None):
+        """Words 0..29 of the accumulators added over the filters with mask != 0 (uint8 / bool [B]; None = all): a float64 device tensor
+        [30] in the order of LAYOUT (n, sum_nis, sum_nis_sq, sum_logdet, n_bad, n_pairs, then sum_nu, sum_nu_sq, sum_S_diag, sum_lag,
+        six each).  Two launches; deterministic, and additive over shards."""
+        from . import devio as _devio
+        io = self.io
+        if mask is not None:
+            io._check_mask(mask, io.ekf.batch)
+        D, Q = _devio.devio_lib(), score_lib()
+        view = io._view()
+        out = io._alloc([(SUMS,)], "float64")[0]
+        with io._ordered(D, view, self.acc, mask):
+            qcheck(Q.qsc_summary(C.byref(view), self.acc.data_ptr(), None if mask is None else mask.data_ptr(), out.data_ptr()))
+        return out
+
+
+def run_host(ekf, inputs, t0, n):
+    """qsc_run_host: ticks [t0, t0 + n) of an `InputSequence`, scored; the accumulators [WORDS, B] as a numpy array."""
+    import numpy as np
+    refuse_multirate(ekf.params)
+    acc = np.zeros((WORDS, ekf.batch))
+    qcheck(score_lib().qsc_run_host(ekf._h, inputs._h, int(t0), int(n), C.byref(ekf.params), acc.ctypes.data_as(C.POINTER(C.c_double))))
+    return acc
