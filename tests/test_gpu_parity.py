@@ -208,6 +208,35 @@ def test_fused_step_equals_predict_then_update(dtype, tol):
     ekf.close()
 
 
+@pytest.mark.parametrize("dtype,tol", [("f64", F64), ("f32", F32)])
+def test_fused_step_equals_predict_then_update_conventional(dtype, tol):
+    """test_fused_step_equals_predict_then_update with direct_orien_method = 0 (the reference constructor's default): ties the fused
+    tick's conventional correction to the stand-alone one that test_gpu_linearisation.py holds to the model-derived truth.  A function
+    of its own: the ids of the direct-only test key rows of tolerances_tight.json."""
+    kw = dict(update_freq=400.0, direct_orien_method=0, **HW)
+    po, pq = both(**kw)
+    rng = np.random.default_rng(7)
+    B = 1000
+    x, P = rand_states(rng, B, 15, cov_scale=0.3)
+    u = rand_imu(rng, B)
+    xr, Pr, _ = oracle_predict_batch(po, x, P, u)
+    z = meas_near(rng, po, xr)
+    mask = (rng.uniform(size=B) < 0.5).astype(np.uint8)
+    xr, Pr, _ = oracle_update_batch(po, xr, Pr, z, mask)
+    ekf = qla.BatchedRelativePoseEKF(B, dtype, params=pq)
+    ekf.set_state(x, P)
+    ekf.step(u, z, mask)
+    xg, Pg = ekf.get_state()
+    assert_state_close(xg, Pg, xr, Pr, **UPD[dtype])
+    # predict-only tick through the same entry point
+    ekf.set_state(x, P)
+    ekf.step(u)
+    xg, Pg = ekf.get_state()
+    xr, Pr, _ = oracle_predict_batch(po, x, P, u)
+    assert_state_close(xg, Pg, xr, Pr, **tol)
+    ekf.close()
+
+
 def test_per_filter_params_cfg5():
     kw = dict(update_freq=400.0, direct_orien_method=1)
     po, pq = both(**kw)
