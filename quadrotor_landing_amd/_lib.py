@@ -176,7 +176,7 @@ def check(rc):
 
 
 def load_side_library(path, symbols, what, needs_tick_library):
-    """Load one of the libraries beside libqle_ekf.so (devio, gate, consistency, health, lookahead, sequence, score) and bind `symbols`, name ->
+    """Load one of the libraries beside libqle_ekf.so (devio, gate, consistency, health, lookahead, sequence, score, bank) and bind `symbols`, name ->
     (restype, argtypes); raises (never falls back) when it is missing.  needs_tick_library: the library takes qle_params_derive from
     the tick library, which is loaded first so that it is the same copy the handle uses (QLE_LIB included)."""
     if not os.path.exists(path):

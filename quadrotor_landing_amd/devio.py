@@ -34,6 +34,10 @@ Innovation scoring for noise sweeps (score.py, libqle_score.so): `scorer()` retu
 `tick`, or `run(seq)` in place of `run`, accumulates every filter's innovation log-likelihood and per-component consistency statistics
 on the GPU -- one read-only launch per tag tick, the ticks themselves unchanged.
 
+Filter banks (bank.py, libqle_bank.so): `bank(M)` reads the handle as B / M banks of M consecutive filters, and `Bank.fuse(logw)` returns
+a `Fused` -- the members' posterior weights and every bank's moment-matched estimate, computed in one read-only launch into a workspace
+of its own and readable through the same calls (`state`, `report`, `health`, `nees`).
+
 Still host-fed through `BatchedRelativePoseEKF`: `set_state` and the per-filter stamps of `dynamic_meas_delay`
 (`filter_update(t_curr=..., apriltag_time=...)`).
 """
@@ -42,6 +46,7 @@ import ctypes as C
 import os
 import sys
 
+from . import bank as _bank
 from . import consistency as _cons
 from . import gate as _gate
 from . import health as _health
@@ -525,6 +530,14 @@ class DeviceIO:
                                          None if mask is None else mask.data_ptr(), workspace.data_ptr(), nbytes, C.byref(ahead),
                                          None if coast is None else C.byref(coast), None if ticks is None else ticks.data_ptr()))
         return _look.Forecast(self, ahead, workspace, h, ticks)
+
+    # ---- filter banks: posterior weights and a fused estimate per bank, read-only
+    def bank(self, members):
+        """The handle read as B / members banks of `members` consecutive filters (a power of two in 2..bank.MAX_MEMBERS that divides B):
+        a `bank.Bank`, whose `fuse(logw, mask=None)` returns a `bank.Fused` -- the members' posterior weights w_i ~ exp(logw_i) and
+        every bank's moment-matched mixture, ONE read-only launch of k_bank_fuse per call.  logw: a float64 device tensor [B], or a
+        `score.Scorer` (its log-likelihood).  The handle is not written; multirate handles included."""
+        return _bank.Bank(self, members)
 
     def _check_mask(self, mask, B, name="mask", shape=None):
         shape = (B,) if shape is None else tuple(shape)

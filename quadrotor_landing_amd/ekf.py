@@ -404,6 +404,35 @@ class BatchedRelativePoseEKF:
         dv._dcheck(D.qdv_signal_stream(C.byref(ahead), stream))
         return x.cpu().numpy(), P.cpu().numpy(), ticks
 
+    def fuse_banks(self, members, logw, mask=None):
+        """The handle read as B / members banks of `members` consecutive filters (`DeviceIO.bank`): the members' posterior weights
+        w_i ~ exp(logw_i) and every bank's moment-matched estimate, without writing the handle (one launch of k_bank_fuse).  Host arrays
+        in and out: logw [B] float64, mask [B] or None (all).  Returns (x [G,16], P [G,n,n], w [B], best [G] int32); an empty bank: zero
+        rows and best = -1."""
+        from . import bank as bk
+        from . import devio as dv
+        from ._lib import QleDeviceView
+        B, n = self.batch, self.num_states
+        M = bk.check_members(members, B)
+        G = B // M
+        lw = _f64(logw, (B,))
+        m = _u8(mask, (B,))
+        K, D = bk.bank_lib(), dv.devio_lib()
+        view = self._device_view()
+        nbytes = bk.bcheck(K.qbk_workspace_bytes(C.byref(view), M))
+        import torch
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        w = np.empty(B); best = np.empty(G, np.int32)
+        fused = QleDeviceView()
+        bk.bcheck(K.qbk_fuse_host(C.byref(view), M, _dp(lw), None if m is None else m.ctypes.data_as(_pu8), workspace.data_ptr(), nbytes,
+                                  C.byref(fused), _dp(w), best.ctypes.data_as(C.POINTER(C.c_int32))))
+        x = torch.empty((G, 16), dtype=torch.float64, device=workspace.device); P = torch.empty((G, n, n), dtype=torch.float64, device=workspace.device)
+        stream = int(torch.cuda.current_stream(self.device).cuda_stream)
+        dv._dcheck(D.qdv_wait_stream(C.byref(fused), stream))
+        dv._dcheck(D.qdv_unpack_state(C.byref(fused), x.data_ptr(), P.data_ptr(), dv.QDV_F64))
+        dv._dcheck(D.qdv_signal_stream(C.byref(fused), stream))
+        return x.cpu().numpy(), P.cpu().numpy(), w, best
+
     # ---- reporting / control
     def report(self):
         """What the node publishes after a tick (relative_pose_EKF_node.cpp:192-220)."""
