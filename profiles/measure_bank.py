@@ -108,7 +108,7 @@ def main():
             io.tick(u, z if k % 4 == 3 else None)
         logw = torch.randn((B,), generator=g, device="cuda:0", dtype=torch.float64) * 2.0
         x_true = io.state(dtype="float64")[0].clone()
-        D, K, N = dv.devio_lib(), bk.bank_lib(), cs.consistency_lib()
+        K, N = bk.bank_lib(), cs.consistency_lib()
         view = io._view()
         nees_out = torch.empty((B,), dtype=torch.float64, device="cuda:0")
 
@@ -127,7 +127,7 @@ def main():
             return statistics.median(us), us[len(us) // 10], us[(9 * len(us)) // 10]
 
         def nees_kernel():
-            with io._ordered(D, view, x_true):
+            with io._ordered(view, x_true):
                 cs.ccheck(N.qcs_nees(C.byref(view), C.byref(ekf.params), x_true.data_ptr(), dv.QDV_F64, None, 31, float("inf"), nees_out.data_ptr(),
                                      None, None, dv.QDV_F64))
 
@@ -140,7 +140,7 @@ def main():
             fused = QleDeviceView()
 
             def fuse_kernel():
-                with io._ordered(D, view, logw):
+                with io._ordered(view, logw):
                     bk.bcheck(K.qbk_fuse(C.byref(view), M, logw.data_ptr(), None, ws.data_ptr(), nbytes, C.byref(fused), w.data_ptr(), best.data_ptr()))
 
             rows = dict(fuse=lambda: b.fuse(logw), fuse_kernel=fuse_kernel, nees=lambda: io.nees(x_true), nees_kernel=nees_kernel,

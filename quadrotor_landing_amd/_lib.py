@@ -150,6 +150,18 @@ SYMBOLS = {
     "qle_launch_census_end": (C.c_int, [C.c_char_p, _i64, C.POINTER(_i64)]),
 }
 
+def _bind(path, symbols, no_fallback):
+    """CDLL(path) with every entry of `symbols`, name -> (restype, argtypes), typed; raises (never falls back) when the file is missing."""
+    if not os.path.exists(path):
+        raise ImportError(f"{path} not built: run `make -C quadrotor_landing_amd/csrc` (hipcc, gfx950). {no_fallback}")
+    L = C.CDLL(path)
+    for name, (res, args) in symbols.items():
+        fn = getattr(L, name)  # AttributeError if the library does not export it
+        fn.restype = res
+        fn.argtypes = args
+    return L
+
+
 _lib = None
 
 
@@ -157,15 +169,7 @@ def lib():
     """Load libqle_ekf.so; raises (never falls back) when it is missing."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not built: run `make -C quadrotor_landing_amd/csrc` "
-                              "(hipcc, gfx950). There is no CPU fallback for the EKF engine.")
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(L, name)  # AttributeError if the library does not export it
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
+        _lib = _bind(LIB_PATH, SYMBOLS, "There is no CPU fallback for the EKF engine.")
     return _lib
 
 
@@ -175,21 +179,35 @@ def check(rc):
     return rc
 
 
-def load_side_library(path, symbols, what, needs_tick_library):
-    """Load one of the libraries beside libqle_ekf.so (devio, gate, consistency, health, lookahead, sequence, score, bank) and bind `symbols`, name ->
-    (restype, argtypes); raises (never falls back) when it is missing.  needs_tick_library: the library takes qle_params_derive from
-    the tick library, which is loaded first so that it is the same copy the handle uses (QLE_LIB included)."""
-    if not os.path.exists(path):
-        raise ImportError(f"{path} not built: run `make -C quadrotor_landing_amd/csrc` (hipcc, gfx950). "
-                          f"There is no fallback for {what}.")
-    if needs_tick_library:
-        lib()
-    L = C.CDLL(path)
-    for name, (res, args) in symbols.items():
-        fn = getattr(L, name)  # AttributeError if the library does not export it
-        fn.restype = res
-        fn.argtypes = args
-    return L
+class SideLibrary:
+    """One of the libraries beside libqle_ekf.so (devio, gate, consistency, health, lookahead, sequence, score, bank): where it is
+    (`env` names the environment variable that overrides the in-tree path), what it exports (`symbols`, name -> (restype, argtypes)),
+    `what` it is for (the error text when it is missing), the name of its `*_last_error`, and what has to be loaded in front of it.
+    needs_tick_library: the library takes qle_params_derive from the tick library, which is loaded first so that it is the same copy
+    the handle uses (QLE_LIB included); `after`: side libraries it links, loaded before either."""
+
+    def __init__(self, stem, env, symbols, what, last_error, needs_tick_library=False, after=()):
+        self.path = os.environ.get(env) or os.path.join(_HERE, f"libqle_{stem}.so")
+        self.symbols, self.what, self.last_error = symbols, what, last_error
+        self.needs_tick_library, self.after = needs_tick_library, tuple(after)
+        self._handle = None
+
+    def load(self):
+        """The bound library, loaded on the first call; raises (never falls back) when it is missing."""
+        if self._handle is None:
+            for other in self.after:
+                other.load()
+            if self.needs_tick_library:
+                lib()
+            self._handle = _bind(self.path, self.symbols, f"There is no fallback for {self.what}.")
+        return self._handle
+
+    def check(self, rc):
+        """rc of one of the library's entries (0, a count, or a negative QLE_ERR_*): raises `QleError` with the library's message for
+        rc < 0 and returns rc otherwise."""
+        if rc < 0:
+            raise QleError(rc, getattr(self.load(), self.last_error)().decode())
+        return rc
 
 
 _cxa = None

@@ -13,12 +13,10 @@ Not provided: `lookahead` of a fused view (which Q a fused estimate coasts under
 per-filter parameters), banks that cross a 64-filter tile, and a member count that is not a power of two.
 """
 import ctypes as C
-import os
 
-from ._lib import QleDeviceView, QleError, load_side_library
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-BANK_LIB_PATH = os.environ.get("QLE_BANK_LIB") or os.path.join(_HERE, "libqle_bank.so")
+from ._lib import QleDeviceView, SideLibrary
+from .records import ViewRecords
+from .score import Scorer
 
 MAX_MEMBERS = 64
 
@@ -34,21 +32,8 @@ SYMBOLS = {
                                 C.POINTER(C.c_int32)]),
 }
 
-_blib = None
-
-
-def bank_lib():
-    """Load libqle_bank.so; raises (never falls back) when it is missing."""
-    global _blib
-    if _blib is None:
-        _blib = load_side_library(BANK_LIB_PATH, SYMBOLS, "the filter-bank kernel", needs_tick_library=False)
-    return _blib
-
-
-def bcheck(rc):
-    if rc < 0:
-        raise QleError(rc, bank_lib().qbk_last_error().decode())
-    return rc
+BANK = SideLibrary("bank", "QLE_BANK_LIB", SYMBOLS, "the filter-bank kernel", "qbk_last_error")
+BANK_LIB_PATH, bank_lib, bcheck = BANK.path, BANK.load, BANK.check
 
 
 def check_members(M, batch):
@@ -63,53 +48,21 @@ def check_members(M, batch):
     return M
 
 
-class _FusedHandle:
-    """What a `DeviceIO` reads of its handle, for the fused view: `batch` is the number of banks, everything else (parameters, dtype,
-    device, num_states) is the handle's.  Never written through."""
-
-    def __init__(self, ekf, banks):
-        self._ekf = ekf
-        self.batch = banks
-
-    def __getattr__(self, name):
-        return getattr(self._ekf, name)
-
-
-class Fused:
+class Fused(ViewRecords):
     """The fused estimate of a `DeviceIO`'s banks: owns the workspace tensor the G records live in and the `qle_device_view` of them.
     `w` [B] (float64): the members' posterior weights, 0 for an invalid member; `best` [G] (int32): the filter index of each bank's
     reference member (the lowest-index valid member of the largest log-weight), -1 for an empty bank, whose record is all zero
-    ("uninitialised" to every consumer).  Nothing here writes a handle; the consumers are the existing read-only bindings, run on the
-    fused view.  `nees` takes its static biases from the handle's shared parameters: the fused view carries no per-filter parameters.
-    There is no `lookahead`: which Q a fused estimate coasts under is a modelling choice."""
+    ("uninitialised" to every consumer).  Nothing here writes a handle; the consumers (`state`, `report`, `health`, `nees`, over G
+    filters) are the read-only bindings of `DeviceRecords`, run on the fused view.  `nees` takes its static biases from the handle's
+    shared parameters: the fused view carries no per-filter parameters.  There is no `lookahead`: which Q a fused estimate coasts
+    under is a modelling choice."""
 
     def __init__(self, io, view, workspace, members, w, best):
-        self.ekf = io.ekf              # the handle the estimate descends from (never written)
         self.members = check_members(members, io.ekf.batch)
         self.banks = io.ekf.batch // self.members
-        self.view = view
-        self.workspace = workspace
+        super().__init__(io.ekf, self.banks, view, workspace)   # the handle the estimate descends from (never written)
         self.w = w
         self.best = best
-        # a DeviceIO over G filters whose view is the fused view: state(), report(), health() and nees() run on it unchanged
-        self._io = type(io)(_FusedHandle(io.ekf, self.banks))
-        self._io._view = lambda: self.view
-
-    def state(self, dtype=None, out=None):
-        """(x [G,16], P [G,n,n]) of the fused estimates as device tensors; an empty bank's rows are zero."""
-        return self._io.state(dtype=dtype, out=out)
-
-    def report(self, dtype=None, out=None):
-        """What the node would publish for every bank (`DeviceIO.report`)."""
-        return self._io.report(dtype=dtype, out=out)
-
-    def health(self, **kw):
-        """`DeviceIO.health` of the fused estimates; empty banks are uninitialised there."""
-        return self._io.health(**kw)
-
-    def nees(self, x_true, **kw):
-        """NEES of the fused estimates against a truth x_true [G,16] (`DeviceIO.nees`)."""
-        return self._io.nees(x_true, **kw)
 
 
 class Bank:
@@ -128,21 +81,18 @@ class Bank:
         Asynchronous, no synchronisation; the handle is not written."""
         io = self.io
         B = io.ekf.batch
-        from . import score as _score
-        if isinstance(logw, _score.Scorer):
+        if isinstance(logw, Scorer):
             logw = logw.result().loglik
         io._check(logw, "logw", (B,), ("float64",))
-        if mask is not None:
-            io._check_mask(mask, B)
-        from . import devio as _dv
-        D, K = _dv.devio_lib(), bank_lib()
+        io._check_mask(mask)
+        K = bank_lib()
         view = io._view()
         nbytes = bcheck(K.qbk_workspace_bytes(C.byref(view), self.members))
         workspace = io._alloc([(nbytes,)], "uint8")[0]
         w = io._alloc([(B,)], "float64")[0]
         best = io._alloc([(self.banks,)], "int32")[0]
         fused = QleDeviceView()
-        with io._ordered(D, view, logw, mask):
+        with io._ordered(view, logw, mask):
             bcheck(K.qbk_fuse(C.byref(view), self.members, logw.data_ptr(), None if mask is None else mask.data_ptr(), workspace.data_ptr(),
                               nbytes, C.byref(fused), w.data_ptr(), best.data_ptr()))
         return Fused(io, fused, workspace, self.members, w, best)

@@ -6,12 +6,8 @@ Both kernels only read the handle.  `DeviceIO.nees` (devio.py) is the caller for
 `synth_nees` (ekf.py) for host arrays.  There is no fallback: a missing library is an error.
 """
 import ctypes as C
-import os
 
-from ._lib import QleDeviceView, QleError, QleParams, load_side_library
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-CONSISTENCY_LIB_PATH = os.environ.get("QLE_CONSISTENCY_LIB") or os.path.join(_HERE, "libqle_consistency.so")
+from ._lib import QleDeviceView, QleParams, SideLibrary
 
 QCS_F32, QCS_F64 = 0, 1
 BLOCKS = {"r": 1, "v": 2, "theta": 4, "ab": 8, "wb": 16}
@@ -35,20 +31,8 @@ SYMBOLS = {
     "qcs_nees_host": (C.c_int, [_pview, _ppar, _pd, _pu8, C.c_uint32, C.c_double, _pd, _pd, C.POINTER(QcsSummary)]),
 }
 
-_clib = None
-
-
-def consistency_lib():
-    """Load libqle_consistency.so; raises (never falls back) when it is missing."""
-    global _clib
-    if _clib is None:
-        _clib = load_side_library(CONSISTENCY_LIB_PATH, SYMBOLS, "the consistency diagnostics", needs_tick_library=True)
-    return _clib
-
-
-def ccheck(rc):
-    if rc != 0:
-        raise QleError(rc, consistency_lib().qcs_last_error().decode())
+CONSISTENCY = SideLibrary("consistency", "QLE_CONSISTENCY_LIB", SYMBOLS, "the consistency diagnostics", "qcs_last_error", needs_tick_library=True)
+CONSISTENCY_LIB_PATH, consistency_lib, ccheck = CONSISTENCY.path, CONSISTENCY.load, CONSISTENCY.check
 
 
 def block_mask(blocks, num_states=15):

@@ -20,8 +20,10 @@ import weakref
 
 import numpy as np
 
+from . import _tensors as _t
 from . import params as _params
-from ._lib import QLE_F32, QLE_F64, QlePolicy, QleSynthCfg, check, lib
+from ._lib import QLE_F32, QLE_F64, QleDeviceView, QlePolicy, QleSynthCfg, check, lib
+from .records import ViewRecords
 
 _pd = C.POINTER(C.c_double)
 _pu8 = C.POINTER(C.c_uint8)
@@ -299,13 +301,6 @@ class BatchedRelativePoseEKF:
         return out
 
     # ---- filter consistency against a truth (include/qle_consistency.h)
-    def _device_view(self):
-        from ._lib import QleDeviceView
-        v = QleDeviceView()
-        v.struct_size = C.sizeof(QleDeviceView)
-        check(lib().qle_get_device_view(self._h, C.byref(v)))
-        return v
-
     def nees(self, x_true, mask=None, blocks="all", chi2_hi=float("inf")):
         """Normalised estimation error squared e^T P^-1 e of every filter against the truth x_true [B,16] (r, v, q xyzw, ab, wb: the
         layout of the state, with the total true biases), e = truth minus estimate in the filter's error-state convention, over all
@@ -320,7 +315,7 @@ class BatchedRelativePoseEKF:
         bits = cs.block_mask(blocks, n)
         chi2_hi = cs.check_chi2_hi(chi2_hi)
         K = cs.consistency_lib()
-        view = self._device_view()
+        view = _t.device_view(self)
         nees = np.empty(B); err = np.empty((B, n)); s = cs.QcsSummary()
         cs.ccheck(K.qcs_nees_host(C.byref(view), C.byref(self.params), _dp(xt), None if m is None else m.ctypes.data_as(_pu8), bits, chi2_hi,
                                   _dp(nees), _dp(err), C.byref(s)))
@@ -335,7 +330,7 @@ class BatchedRelativePoseEKF:
         The generator's bias truth is the unknown part of the IMU bias; the total true bias adds the static (known) biases, per filter
         where per-filter parameters are in force."""
         pose, bias = self.synth_truth(inputs)
-        if self._device_view().filter_params:
+        if _t.device_view(self).filter_params:
             static = self.get_filter_params()[:, 12:18]
         else:
             static = np.array(list(self.params.ab_static) + list(self.params.wb_static))[None, :]
@@ -366,7 +361,7 @@ class BatchedRelativePoseEKF:
         m = _u8(mask, (B,))
         lim = hl.make_limits(sigma_r_max, sigma_v_max, sigma_theta_max, qnorm_tol, select)
         H = hl.health_lib()
-        view = self._device_view()
+        view = _t.device_view(self)
         status = np.zeros(B, np.uint8); flagged = np.zeros(B, np.uint8); s = hl.QhlSummary()
         hl.hcheck(H.qhl_health_host(C.byref(view), C.byref(lim), None if m is None else m.ctypes.data_as(_pu8), status.ctypes.data_as(_pu8),
                                     flagged.ctypes.data_as(_pu8), C.byref(s)))
@@ -379,29 +374,22 @@ class BatchedRelativePoseEKF:
         """State and covariance h ticks ahead with the IMU sample u [B,6] held: what h calls of `predict(u)` would leave, without
         writing the handle (one launch of k_lookahead; arguments: `DeviceIO.lookahead`).  Host arrays in and out.  Returns
         (x [B,16], P [B,n,n], ticks_to_limit [B] int32 or None when no limit is given); skipped filters: zero rows, -1."""
-        from . import devio as dv
         from . import lookahead as lk
-        from ._lib import QleDeviceView
-        B, n = self.batch, self.num_states
+        B = self.batch
         uu = _f64(u, (B, 6))
         h = lk.check_horizon(h)
         m = _u8(mask, (B,))
         coast = lk.make_coast(sigma_r_max, sigma_theta_max)
-        K, D = lk.lookahead_lib(), dv.devio_lib()
-        view = self._device_view()
+        K = lk.lookahead_lib()
+        view = _t.device_view(self)
         nbytes = lk.kcheck(K.qlk_workspace_bytes(C.byref(view)))
-        import torch
-        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        workspace = _t.empty(self.device, (nbytes,), "uint8")
         ticks = np.empty(B, np.int32) if coast is not None else None
         ahead = QleDeviceView()
         lk.kcheck(K.qlk_lookahead_host(C.byref(view), C.byref(self.params), _dp(uu), h, None if m is None else m.ctypes.data_as(_pu8),
                                        workspace.data_ptr(), nbytes, C.byref(ahead), None if coast is None else C.byref(coast),
                                        None if ticks is None else ticks.ctypes.data_as(C.POINTER(C.c_int32))))
-        x = torch.empty((B, 16), dtype=torch.float64, device=workspace.device); P = torch.empty((B, n, n), dtype=torch.float64, device=workspace.device)
-        stream = int(torch.cuda.current_stream(self.device).cuda_stream)
-        dv._dcheck(D.qdv_wait_stream(C.byref(ahead), stream))
-        dv._dcheck(D.qdv_unpack_state(C.byref(ahead), x.data_ptr(), P.data_ptr(), dv.QDV_F64))
-        dv._dcheck(D.qdv_signal_stream(C.byref(ahead), stream))
+        x, P = ViewRecords(self, B, ahead, workspace).state(dtype="float64")
         return x.cpu().numpy(), P.cpu().numpy(), ticks
 
     def fuse_banks(self, members, logw, mask=None):
@@ -410,27 +398,20 @@ class BatchedRelativePoseEKF:
         in and out: logw [B] float64, mask [B] or None (all).  Returns (x [G,16], P [G,n,n], w [B], best [G] int32); an empty bank: zero
         rows and best = -1."""
         from . import bank as bk
-        from . import devio as dv
-        from ._lib import QleDeviceView
-        B, n = self.batch, self.num_states
+        B = self.batch
         M = bk.check_members(members, B)
         G = B // M
         lw = _f64(logw, (B,))
         m = _u8(mask, (B,))
-        K, D = bk.bank_lib(), dv.devio_lib()
-        view = self._device_view()
+        K = bk.bank_lib()
+        view = _t.device_view(self)
         nbytes = bk.bcheck(K.qbk_workspace_bytes(C.byref(view), M))
-        import torch
-        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        workspace = _t.empty(self.device, (nbytes,), "uint8")
         w = np.empty(B); best = np.empty(G, np.int32)
         fused = QleDeviceView()
         bk.bcheck(K.qbk_fuse_host(C.byref(view), M, _dp(lw), None if m is None else m.ctypes.data_as(_pu8), workspace.data_ptr(), nbytes,
                                   C.byref(fused), _dp(w), best.ctypes.data_as(C.POINTER(C.c_int32))))
-        x = torch.empty((G, 16), dtype=torch.float64, device=workspace.device); P = torch.empty((G, n, n), dtype=torch.float64, device=workspace.device)
-        stream = int(torch.cuda.current_stream(self.device).cuda_stream)
-        dv._dcheck(D.qdv_wait_stream(C.byref(fused), stream))
-        dv._dcheck(D.qdv_unpack_state(C.byref(fused), x.data_ptr(), P.data_ptr(), dv.QDV_F64))
-        dv._dcheck(D.qdv_signal_stream(C.byref(fused), stream))
+        x, P = ViewRecords(self, G, fused, workspace).state(dtype="float64")
         return x.cpu().numpy(), P.cpu().numpy(), w, best
 
     # ---- reporting / control

@@ -6,12 +6,8 @@ mask word of the tick's tag record where NIS = delta_y^T S^-1 delta_y, evaluated
 an error.
 """
 import ctypes as C
-import os
 
-from ._lib import QleDeviceView, QleError, QleInputsView, QleParams, load_side_library
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-GATE_LIB_PATH = os.environ.get("QLE_GATE_LIB") or os.path.join(_HERE, "libqle_gate.so")
+from ._lib import QLE_ERR_STATE, QleDeviceView, QleError, QleInputsView, QleParams, SideLibrary
 
 QGT_F32, QGT_F64 = 0, 1
 _vp = C.c_void_p
@@ -24,17 +20,19 @@ SYMBOLS = {
     "qgt_launch_count": (C.c_int64, []),
 }
 
-_glib = None
+GATE = SideLibrary("gate", "QLE_GATE_LIB", SYMBOLS, "the gate in front of the fused tick", "qgt_last_error", needs_tick_library=True)
+GATE_LIB_PATH, gate_lib, gcheck = GATE.path, GATE.load, GATE.check
 
 
-def gate_lib():
-    """Load libqle_gate.so; raises (never falls back) when it is missing."""
-    global _glib
-    if _glib is None:
-        _glib = load_side_library(GATE_LIB_PATH, SYMBOLS, "the gate in front of the fused tick", needs_tick_library=True)
-    return _glib
+def check_chi2_max(chi2_max):
+    """The gate's threshold as a float > 0 (inf accepts every finite NIS; NaN refused)."""
+    chi2_max = float(chi2_max)
+    if not chi2_max > 0.0:
+        raise ValueError(f"chi2_max must be > 0 (got {chi2_max})")
+    return chi2_max
 
 
-def gcheck(rc):
-    if rc != 0:
-        raise QleError(rc, gate_lib().qgt_last_error().decode())
+def refuse_multirate(params, what="the gate"):
+    """The gate and everything else that evaluates an innovation against the stored state is refused with multirate_ekf."""
+    if params.multirate_ekf:
+        raise QleError(QLE_ERR_STATE, f"{what} does not support multirate_ekf: a delayed measurement's innovation belongs to a history entry")

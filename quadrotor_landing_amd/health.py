@@ -8,12 +8,8 @@ callers for device tensors, `BatchedRelativePoseEKF.health` (ekf.py) for host ar
 error.
 """
 import ctypes as C
-import os
 
-from ._lib import QleDeviceView, QleError, load_side_library
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HEALTH_LIB_PATH = os.environ.get("QLE_HEALTH_LIB") or os.path.join(_HERE, "libqle_health.so")
+from ._lib import QleDeviceView, SideLibrary
 
 NONFINITE, NOT_PD, QNORM, SIGMA_R, SIGMA_V, SIGMA_THETA = 1, 2, 4, 8, 16, 32
 ALL = 63
@@ -45,20 +41,8 @@ SYMBOLS = {
     "qhl_and_masks": (C.c_int, [_pview, _vp, _vp, _vp]),
 }
 
-_hlib = None
-
-
-def health_lib():
-    """Load libqle_health.so; raises (never falls back) when it is missing."""
-    global _hlib
-    if _hlib is None:
-        _hlib = load_side_library(HEALTH_LIB_PATH, SYMBOLS, "the lifecycle kernels", needs_tick_library=False)
-    return _hlib
-
-
-def hcheck(rc):
-    if rc != 0:
-        raise QleError(rc, health_lib().qhl_last_error().decode())
+HEALTH = SideLibrary("health", "QLE_HEALTH_LIB", SYMBOLS, "the lifecycle kernels", "qhl_last_error")
+HEALTH_LIB_PATH, health_lib, hcheck = HEALTH.path, HEALTH.load, HEALTH.check
 
 
 def select_mask(select):

@@ -8,12 +8,10 @@ the caller for device tensors, `BatchedRelativePoseEKF.lookahead` (ekf.py) for h
 is an error.
 """
 import ctypes as C
-import os
 
-from ._lib import QleDeviceView, QleError, QleParams, load_side_library
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LOOKAHEAD_LIB_PATH = os.environ.get("QLE_LOOKAHEAD_LIB") or os.path.join(_HERE, "libqle_lookahead.so")
+from . import _tensors as _t
+from ._lib import QleDeviceView, QleParams, SideLibrary
+from .records import ViewRecords
 
 QLK_F32, QLK_F64 = 0, 1
 MAX_HORIZON = 4096
@@ -36,21 +34,8 @@ SYMBOLS = {
                                      C.POINTER(C.c_int32)]),
 }
 
-_klib = None
-
-
-def lookahead_lib():
-    """Load libqle_lookahead.so; raises (never falls back) when it is missing."""
-    global _klib
-    if _klib is None:
-        _klib = load_side_library(LOOKAHEAD_LIB_PATH, SYMBOLS, "the look-ahead kernel", needs_tick_library=True)
-    return _klib
-
-
-def kcheck(rc):
-    if rc < 0:
-        raise QleError(rc, lookahead_lib().qlk_last_error().decode())
-    return rc
+LOOKAHEAD = SideLibrary("lookahead", "QLE_LOOKAHEAD_LIB", SYMBOLS, "the look-ahead kernel", "qlk_last_error", needs_tick_library=True)
+LOOKAHEAD_LIB_PATH, lookahead_lib, kcheck = LOOKAHEAD.path, LOOKAHEAD.load, LOOKAHEAD.check
 
 
 def check_horizon(h):
@@ -79,39 +64,39 @@ def make_coast(sigma_r_max=float("inf"), sigma_theta_max=float("inf")):
     return c
 
 
-class Forecast:
+class Forecast(ViewRecords):
     """The forecast of a `DeviceIO` (or of another `Forecast`) h ticks ahead: owns the workspace tensor the records live in and the
     `qle_device_view` of them.  `ticks_to_limit`: a device int32 tensor [B] (the coast budget), or None when no limit was given.
-    Nothing here writes a handle; the consumers are the existing read-only bindings, run on the forecast view."""
+    Nothing here writes a handle; the consumers (`state`, `report`, `health`, `nees`) are the read-only bindings of `DeviceRecords`,
+    run on the forecast view."""
 
     def __init__(self, io, view, workspace, h, ticks_to_limit):
-        self.ekf = io.ekf              # parameters, batch, device: the handle the forecast descends from (never written)
-        self.view = view
-        self.workspace = workspace
+        super().__init__(io.ekf, io.ekf.batch, view, workspace)   # the handle the forecast descends from (never written)
         self.h = h
         self.ticks_to_limit = ticks_to_limit
-        # a DeviceIO whose view is the forecast view: state(), report(), health(), nees() and lookahead() run on it unchanged
-        self._io = type(io)(io.ekf)
-        self._io._view = lambda: self.view
-
-    def state(self, dtype=None, out=None):
-        """(x [B,16], P [B,n,n]) of the forecast as device tensors; a skipped filter's rows are zero."""
-        return self._io.state(dtype=dtype, out=out)
-
-    def report(self, dtype=None, out=None):
-        """What the node would publish at the horizon (`DeviceIO.report`)."""
-        return self._io.report(dtype=dtype, out=out)
-
-    def health(self, **kw):
-        """Which filters will be flagged at the horizon (`DeviceIO.health`); skipped filters are uninitialised there."""
-        return self._io.health(**kw)
-
-    def nees(self, x_true, **kw):
-        """NEES of the forecast against a truth at the horizon (`DeviceIO.nees`)."""
-        return self._io.nees(x_true, **kw)
 
     def lookahead(self, u, h, mask=None, sigma_r_max=float("inf"), sigma_theta_max=float("inf")):
         """h more ticks from this forecast: the bits of one call over the sum of the horizons."""
-        f = self._io.lookahead(u, h, mask=mask, sigma_r_max=sigma_r_max, sigma_theta_max=sigma_theta_max)
+        f = forecast(self, u, h, mask, sigma_r_max, sigma_theta_max)
         f.h += self.h
         return f
+
+
+def forecast(rec, u, h, mask=None, sigma_r_max=float("inf"), sigma_theta_max=float("inf")):
+    """`DeviceIO.lookahead` / `Forecast.lookahead`: the records of `rec` (a `DeviceRecords`) h ticks ahead, as a `Forecast`."""
+    B = rec.batch
+    src = rec._check(u, "u", (B, 6))
+    h = check_horizon(h)
+    rec._check_mask(mask)
+    coast = make_coast(sigma_r_max, sigma_theta_max)
+    K = lookahead_lib()
+    view = rec._view()
+    nbytes = kcheck(K.qlk_workspace_bytes(C.byref(view)))
+    workspace = rec._alloc([(nbytes,)], "uint8")[0]
+    ticks = rec._alloc([(B,)], "int32")[0] if coast is not None else None
+    ahead = QleDeviceView()
+    with rec._ordered(view, u, mask):
+        kcheck(K.qlk_lookahead(C.byref(view), C.byref(rec.ekf.params), u.data_ptr(), _t.FLOATS[src], h,
+                               None if mask is None else mask.data_ptr(), workspace.data_ptr(), nbytes, C.byref(ahead),
+                               None if coast is None else C.byref(coast), None if ticks is None else ticks.data_ptr()))
+    return Forecast(rec, ahead, workspace, h, ticks)

@@ -9,12 +9,11 @@ is an error.
 """
 import ctypes as C
 import math
-import os
 
-from ._lib import QLE_ERR_STATE, QleDeviceView, QleError, QleInputsView, QleParams, load_side_library
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-SCORE_LIB_PATH = os.environ.get("QLE_SCORE_LIB") or os.path.join(_HERE, "libqle_score.so")
+from . import _tensors as _t
+from . import gate as _gate
+from ._lib import QleDeviceView, QleInputsView, QleParams, SideLibrary
+from .sequence import DeviceSequence
 
 WORDS, SUMS = 40, 30   # QSC_WORDS, QSC_SUMS
 # the words of an accumulator record: name -> (first word, count)
@@ -34,25 +33,8 @@ SYMBOLS = {
     "qsc_run_host": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _ppar, C.POINTER(C.c_double)]),
 }
 
-_qlib = None
-
-
-def score_lib():
-    """Load libqle_score.so; raises (never falls back) when it is missing."""
-    global _qlib
-    if _qlib is None:
-        _qlib = load_side_library(SCORE_LIB_PATH, SYMBOLS, "innovation scoring", needs_tick_library=True)
-    return _qlib
-
-
-def qcheck(rc):
-    if rc != 0:
-        raise QleError(rc, score_lib().qsc_last_error().decode())
-
-
-def refuse_multirate(params):
-    if params.multirate_ekf:
-        raise QleError(QLE_ERR_STATE, "scoring does not support multirate_ekf: a delayed measurement's innovation belongs to a history entry")
+SCORE = SideLibrary("score", "QLE_SCORE_LIB", SYMBOLS, "innovation scoring", "qsc_last_error", needs_tick_library=True)
+SCORE_LIB_PATH, score_lib, qcheck = SCORE.path, SCORE.load, SCORE.check
 
 
 class Score:
@@ -79,11 +61,10 @@ class Scorer:
     [WORDS, padded batch] (float64, include/qle_score.h) on the handle's GPU.  Every call is asynchronous and none synchronises."""
 
     def __init__(self, io):
-        import torch
-        refuse_multirate(io.ekf.params)
+        _gate.refuse_multirate(io.ekf.params, "scoring")
         self.io = io
         self._Bp = -(-io.ekf.batch // 64) * 64
-        self.acc = torch.zeros((WORDS, self._Bp), dtype=torch.float64, device=torch.device("cuda", io.ekf.device))
+        self.acc = _t.empty(io.ekf.device, (WORDS, self._Bp), "float64", zero=True)
 
     def reset(self):
         self.acc.zero_()
@@ -92,39 +73,30 @@ class Scorer:
         """Score the tag poses of the tick `io.tick(u, z, mask)` is about to run -- call it BEFORE that tick: packs u [B,6], z [B,7] and
         mask [B] (uint8 / bool; None = all) into the slot the tick will pack again, and adds every filter's innovation against the
         predicted state to its accumulators.  One pack and ONE launch of k_score; the state is not touched."""
-        from . import devio as _devio
         io = self.io
         B = io.ekf.batch
-        src = io._check(u, "u", (B, 6), _devio._FLOATS)
-        if io._check(z, "z", (B, 7), _devio._FLOATS) != src:
+        src = io._check(u, "u", (B, 6))
+        if io._check(z, "z", (B, 7)) != src:
             raise ValueError("u and z must have the same dtype")
-        if mask is not None:
-            io._check_mask(mask, B)
-        refuse_multirate(io.ekf.params)
-        D, Q = _devio.devio_lib(), score_lib()
+        io._check_mask(mask)
+        _gate.refuse_multirate(io.ekf.params, "scoring")
+        D, Q = _t.devio_lib(), score_lib()
         view = io._view()
         iv = io._inputs_view(1)
-        with io._ordered(D, view, u, z, mask, self.acc):
-            _devio._dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), u.data_ptr(), z.data_ptr(), None if mask is None else mask.data_ptr(),
-                                             _devio._FLOATS[src]))
+        with io._ordered(view, u, z, mask, self.acc):
+            _t.dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), u.data_ptr(), z.data_ptr(), None if mask is None else mask.data_ptr(),
+                                        _t.FLOATS[src]))
             qcheck(Q.qsc_score_tick(C.byref(view), C.byref(iv), C.byref(io.ekf.params), self.acc.data_ptr()))
 
     def run(self, seq, t0=0, n=None):
         """Ticks [t0, t0 + n) of a `DeviceSequence` (n None: to its end), scored, in ONE native call (qsc_run): what `io.run(seq, t0, n)`
         does -- state and sequence end with its bits -- with k_score in front of every tick that has a tag slot."""
-        from . import devio as _devio
-        from . import sequence as _seqm
         io = self.io
-        if not isinstance(seq, _seqm.DeviceSequence) or seq.io.ekf is not io.ekf or seq.inputs is None:
-            raise ValueError("seq: expected an open DeviceSequence made by this handle's DeviceIO.sequence")
-        t0 = int(t0)
-        n = seq.n_ticks - t0 if n is None else int(n)
-        if t0 < 0 or n < 0 or t0 + n > seq.n_ticks:
-            raise ValueError(f"ticks [{t0}, {t0 + n}) reach beyond the sequence of {seq.n_ticks} ticks")
-        refuse_multirate(io.ekf.params)
-        D, Q = _devio.devio_lib(), score_lib()
+        t0, n = DeviceSequence.window(io, seq, t0, n)
+        _gate.refuse_multirate(io.ekf.params, "scoring")
+        Q = score_lib()
         view = io._view()
-        with io._ordered(D, view, self.acc):
+        with io._ordered(view, self.acc):
             qcheck(Q.qsc_run(io.ekf._h, seq.inputs._h, t0, n, C.byref(io.ekf.params), self.acc.data_ptr()))
 
     def result(self):
@@ -135,14 +107,12 @@ class Scorer:
         """Words 0..29 of the accumulators added over the filters with mask != 0 (uint8 / bool [B]; None = all): a float64 device tensor
         [30] in the order of LAYOUT (n, sum_nis, sum_nis_sq, sum_logdet, n_bad, n_pairs, then sum_nu, sum_nu_sq, sum_S_diag, sum_lag,
         six each).  Two launches; deterministic, and additive over shards."""
-        from . import devio as _devio
         io = self.io
-        if mask is not None:
-            io._check_mask(mask, io.ekf.batch)
-        D, Q = _devio.devio_lib(), score_lib()
+        io._check_mask(mask)
+        Q = score_lib()
         view = io._view()
         out = io._alloc([(SUMS,)], "float64")[0]
-        with io._ordered(D, view, self.acc, mask):
+        with io._ordered(view, self.acc, mask):
             qcheck(Q.qsc_summary(C.byref(view), self.acc.data_ptr(), None if mask is None else mask.data_ptr(), out.data_ptr()))
         return out
 
@@ -150,7 +120,7 @@ class Scorer:
 def run_host(ekf, inputs, t0, n):
     """qsc_run_host: ticks [t0, t0 + n) of an `InputSequence`, scored; the accumulators [WORDS, B] as a numpy array."""
     import numpy as np
-    refuse_multirate(ekf.params)
+    _gate.refuse_multirate(ekf.params, "scoring")
     acc = np.zeros((WORDS, ekf.batch))
     qcheck(score_lib().qsc_run_host(ekf._h, inputs._h, int(t0), int(n), C.byref(ekf.params), acc.ctypes.data_as(C.POINTER(C.c_double))))
     return acc

@@ -23,6 +23,7 @@ import bank_util as bu
 import test_variant_table_cpu as tv
 from quadrotor_landing_amd import _lib, bank, devio
 from test_devio_cpu import FakeTensor, _kernels, _needed
+from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
@@ -169,11 +170,7 @@ class FakeEkf:
 
 
 def test_python_refuses_a_bad_geometry_before_any_native_call(monkeypatch):
-    def boom(*a, **k):
-        raise AssertionError("a native library was reached")
-    monkeypatch.setattr(devio, "devio_lib", boom)
-    monkeypatch.setattr(devio, "lib", boom)
-    monkeypatch.setattr(bank, "bank_lib", boom)
+    forbid_native(monkeypatch)
     io = devio.DeviceIO(FakeEkf())
     for bad in (0, 1, 3, 6, 48, 128, -4, 2.5, 4.0 + 1e-9, True, "4", None):
         with pytest.raises(ValueError):

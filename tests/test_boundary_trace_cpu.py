@@ -1,0 +1,280 @@
+"""The Python device boundary as the native libraries see it, without a GPU: every public call of `DeviceIO`, `DeviceSequence`,
+`Scorer`, `Forecast`, `Bank` / `Fused` and the host-array `lookahead` / `fuse_banks` is made once per meaningful option set against
+recording stubs of the tick library and the eight side libraries, and the ordered list of (library, function, arguments) is compared
+with tests/golden/boundary_trace.json.  A pointer argument is recorded as the name of the fake tensor (or handle) it points to, a
+struct with its fields.  The golden was recorded from the commit BEFORE the boundary was restructured, so equality says that the
+restructuring changed no native call, no argument and no ordering of one."""
+import ctypes as C
+import json
+import os
+import types
+
+import numpy as np
+
+import quadrotor_landing_amd as qla
+from quadrotor_landing_amd import _lib, bank, consistency, devio, gate, health, lookahead, score, sequence
+from test_devio_cpu import FakeTensor
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "boundary_trace.json")
+STREAM = 0x5000         # the caller's current stream
+WORKSPACE = 4096        # what every *_workspace_bytes answers
+
+
+class Tensor(FakeTensor):
+    """A FakeTensor with the arithmetic `score.Score` does on the accumulators: every result is a fresh float64 tensor named "derived"."""
+    rec = None
+
+    def _derived(self, other=None):
+        shape = other.shape if isinstance(other, FakeTensor) and len(other.shape) > len(self.shape) else self.shape
+        return Tensor(shape, "float64", self.device, ptr=self.rec.ptr("derived"))
+
+    __add__ = __radd__ = __mul__ = __rmul__ = __truediv__ = _derived
+
+    @property
+    def T(self):
+        return Tensor(self.shape[::-1], self.dtype, self.device, ptr=self.rec.ptr("derived"))
+
+    def cpu(self):
+        return self
+
+    def numpy(self):
+        return np.zeros(self.shape)
+
+
+class Recorder:
+    def __init__(self, record=True):
+        self.trace, self.names, self.record = [], {}, record
+        self.next_ptr, self.label, self.count, self.slots = 0x7F0000000000, "", {}, {}
+
+    def mark(self, label):
+        """What follows belongs to this public call; the tensors it allocates are numbered from 1 again."""
+        self.label, self.count = label, {}
+        self.trace.append(["--", label, []])
+
+    def ptr(self, name):
+        self.next_ptr += 0x100000
+        self.names[self.next_ptr] = name
+        return self.next_ptr
+
+    def tensor(self, name, shape, dtype="float32"):
+        return Tensor(shape, dtype, ptr=self.ptr(name))
+
+    def alloc(self, shape, dn, zero=False):
+        shape = [int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,))]
+        key = f"{self.label}/{dn}{shape}{'=0' if zero else ''}"
+        self.count[key] = self.count.get(key, 0) + 1
+        return self.tensor(f"{key}#{self.count[key]}", shape, dn)
+
+    def enc(self, v):
+        if v is None or isinstance(v, (bool, str, float)):
+            return v
+        if isinstance(v, int):
+            return self.names.get(v, v)
+        if type(v).__name__ == "CArgObject":   # C.byref(x)
+            return self.enc(v._obj)
+        if isinstance(v, _lib.QleParams):
+            return self.names.get(C.addressof(v), "params of no handle")
+        if isinstance(v, C.Structure):
+            return {"struct": type(v).__name__, **{f[0]: self.enc(getattr(v, f[0])) for f in v._fields_}}
+        if isinstance(v, C._Pointer):
+            if not v:
+                return None
+            return self.enc(v.contents) if isinstance(v.contents, C.Structure) else f"host {type(v).__name__}"
+        if isinstance(v, C.Array):
+            return [self.enc(x) for x in v]
+        if isinstance(v, C._SimpleCData):
+            return self.enc(v.value)
+        raise TypeError(f"cannot record {v!r}")
+
+
+def _ceil64(b):
+    return -(-b // 64) * 64
+
+
+class Stub:
+    """A native library: every entry records its call and returns 0 (a fixed size for *_workspace_bytes, b"" for *_last_error); the
+    entries that fill a view fill it with fixed values."""
+
+    def __init__(self, rec, lib):
+        self.rec, self.lib = rec, lib
+
+    def __getattr__(self, fn):
+        def call(*a):
+            if self.rec.record:
+                self.rec.trace.append([self.lib, fn, [self.rec.enc(x) for x in a]])
+            return self.reply(fn, a)
+        self.__dict__[fn] = call
+        return call
+
+    def reply(self, fn, a):
+        rec = self.rec
+        if fn.endswith("_last_error"):
+            return b""
+        if fn.endswith("_workspace_bytes"):
+            return WORKSPACE
+        if fn == "qle_get_device_view":
+            h = a[0].value if isinstance(a[0], C.c_void_p) else a[0]
+            ekf, v = rec.handles[h], a[1]._obj
+            v.struct_size, v.device, v.stream, v.dtype, v.num_states = C.sizeof(v), 0, 0x1000, ekf.dtype, ekf.num_states
+            v.batch, v.padded_batch, v.state, v.state_words, v.record_words = ekf.batch, _ceil64(ekf.batch), ekf.state, 144, 136
+        elif fn == "qle_inputs_get_device_view":
+            if (a[0], a[1]) not in rec.slots:
+                rec.slots[a[0], a[1]] = [rec.ptr(f"{rec.names[a[0]]}.{w}{a[1]}") for w in "uz"]
+            iv = a[2]._obj
+            iv.struct_size, iv.has_tag, (iv.u, iv.z) = C.sizeof(iv), a[1], rec.slots[a[0], a[1]]
+        elif fn in ("qlk_lookahead", "qlk_lookahead_host", "qbk_fuse", "qbk_fuse_host"):
+            ws, out = {"qlk_lookahead": (6, 8), "qlk_lookahead_host": (5, 7), "qbk_fuse": (4, 6), "qbk_fuse_host": (4, 6)}[fn]
+            src, dst = a[0]._obj, a[out]._obj
+            C.memmove(C.addressof(dst), C.addressof(src), C.sizeof(dst))
+            dst.state = a[ws]
+            if fn.startswith("qbk"):
+                dst.batch = src.batch // a[1]
+                dst.padded_batch = _ceil64(dst.batch)
+        return 0
+
+
+class FakeInputs:
+    def __init__(self, rec, name):
+        self.rec, self.name, self._h = rec, name, rec.ptr(name)
+
+    def close(self):
+        self.rec.trace.append(["handle", "inputs.close", [self.name]])
+
+
+class FakeEkf:
+    device = 0
+
+    def __init__(self, rec, batch, dtype, num_states):
+        self.rec, self.batch, self.dtype, self.num_states = rec, batch, dtype, num_states
+        self._h, self.state, self.params, self.made = rec.ptr(f"handle{batch}"), rec.ptr(f"state{batch}"), _lib.QleParams(), 0
+        rec.names[C.addressof(self.params)] = f"params{batch}"
+        rec.handles[self._h] = self
+
+    def make_inputs(self, n_ticks, tick_has_meas=None):
+        self.made += 1
+        self.rec.trace.append(["handle", "make_inputs", [self.batch, int(n_ticks), [int(t) for t in tick_has_meas]]])
+        return FakeInputs(self.rec, f"inputs{self.batch}#{self.made}")
+
+
+def drive(rec):
+    """Every public call of the boundary, once per meaningful option set."""
+    rec.handles = {}
+    Tensor.rec = rec
+    T, mark, inf = rec.tensor, rec.mark, float("inf")
+    B, K, ticks = 100, 40, [1, 3, 9]
+    ekf = FakeEkf(rec, B, _lib.QLE_F32, 15)      # ragged: padded to 128
+    io = devio.DeviceIO(ekf)
+    u, z, m, x_true = T("u", (B, 6)), T("z", (B, 7)), T("mask", (B,), "uint8"), T("x_true", (B, 16))
+    mark("tick"); io.tick(u)
+    mark("tick tag"); io.tick(u, z)
+    mark("tick mask"); io.tick(u, z, m)
+    mark("tick gated"); assert io.tick(u, z, m, chi2_max=16.81).shape == (B,)
+    mark("tick gated nis"); assert len(io.tick(u, z, chi2_max=inf, return_nis=True)) == 4
+    mark("innovation"); io.innovation(z)
+    mark("innovation mask f64"); io.innovation(T("z64", (B, 7), "float64"), m, dtype="float64")
+    mark("nees"); assert len(io.nees(x_true)) == 2
+    mark("nees err"); assert len(io.nees(x_true, m, blocks="pose", chi2_hi=12.59, return_err=True, dtype="float64")) == 3
+    mark("seed"); io.seed(z)
+    mark("seed mask"); io.seed(z, m, reinit_bias=True)
+    mark("health"); assert len(io.health()) == 2
+    mark("health summary")
+    assert len(io.health(mask=m, sigma_r_max=2.0, sigma_v_max=3.0, sigma_theta_max=0.5, qnorm_tol=1e-4, select="nonfinite+not_pd", return_summary=True)) == 3
+    mark("retire"); io.retire(m)
+    mark("reseed"); io.reseed(z)
+    mark("reseed mask"); io.reseed(z, m, reinit_bias=False, sigma_r_max=2.0, select=3)
+    mark("state"); io.state()
+    mark("state f64"); io.state(dtype="float64")
+    mark("state out"); io.state(out=(T("x_out", (B, 16)), T("P_out", (B, 15, 15))))
+    mark("report"); io.report()
+    mark("report out"); io.report(out={"pose": T("pose_out", (B, 7), "float64"), "vel": T("vel_out", (B, 3), "float64")})
+    # a whole sequence per call
+    mark("sequence"); seq = io.sequence(T("u_seq", (K, B, 6)), T("z_seq", (3, B, 7)), ticks, T("mask_seq", (3, B), "uint8"))
+    mark("sequence no tags"); bare = io.sequence(T("u_bare", (7, B, 6)))
+    mark("pack"); seq.pack(T("u_win", (10, B, 6)), T("z_win", (2, B, 7)), t0=2)
+    mark("run"); io.run(seq)
+    mark("run gated nis"); r = io.run(seq, chi2_max=16.81, return_nis=True); assert r.accepted.shape == r.nis.shape == (3, B)
+    mark("run trace report"); r = io.run(seq, trace_every=5); assert r.report["pose_cov"].shape == (8, B, 6, 6)
+    mark("run trace nees")
+    r = io.run(seq, 5, 30, trace_every=5, trace=("nees",), x_true_seq=T("x_true_6", (6, B, 16)), blocks="r+theta", chi2_hi=9.0, dtype="float64")
+    assert r.nees.shape == (6, B) and r.summary.shape == (6, 8) and r.report is None
+    mark("run trace both gated")
+    io.run(seq, trace_every=5, trace=("report", "nees"), x_true_seq=T("x_true_8", (8, B, 16), "float64"), chi2_max=22.46)
+    mark("run J=0"); io.run(seq, 0, 3, trace_every=5, trace=("report", "nees"), x_true_seq=T("x_true_0", (0, B, 16)))
+    # innovation scoring
+    mark("scorer"); sc = io.scorer()
+    mark("observe"); sc.observe(u, z)
+    mark("observe mask"); sc.observe(u, z, m)
+    mark("scorer run"); sc.run(seq)
+    mark("scorer run window"); sc.run(seq, 4, 20)
+    mark("scorer result"); assert sc.result().loglik.shape == (B,) and sc.result().var_ratio.shape == (B, 6)
+    mark("scorer summary"); sc.summary()
+    mark("scorer summary mask"); sc.summary(m)
+    sc.reset()
+    # look-ahead and the consumers on a forecast
+    mark("lookahead"); f = io.lookahead(u, 8)
+    mark("lookahead coast"); fc = io.lookahead(u, 16, mask=m, sigma_r_max=2.0, sigma_theta_max=0.5)
+    assert f.ticks_to_limit is None and fc.ticks_to_limit.shape == (B,) and f.ekf is ekf and f.view.state != io._view().state
+    mark("forecast state"); f.state()
+    mark("forecast report"); f.report(dtype="float64")
+    mark("forecast health"); f.health(sigma_r_max=2.0)
+    mark("forecast nees"); f.nees(x_true, blocks="pose")
+    mark("forecast lookahead"); g = f.lookahead(u, 4, sigma_r_max=2.0); assert g.h == 12
+    mark("forecast of forecast state"); g.state()
+    # banks: B = 128, fp64, 9 states
+    ekf2 = FakeEkf(rec, 128, _lib.QLE_F64, 9)
+    io2 = devio.DeviceIO(ekf2)
+    logw, m2 = T("logw", (128,), "float64"), T("mask128", (128,), "bool")
+    mark("bank fuse"); b = io2.bank(4); fz = b.fuse(logw)
+    mark("bank fuse mask"); b.fuse(logw, m2)
+    mark("bank scorer"); sc2 = io2.scorer()
+    mark("bank fuse scorer"); b.fuse(sc2)
+    assert (fz.members, fz.banks, fz.w.shape, fz.best.shape) == (4, 32, (128,), (32,)) and fz.ekf is ekf2 and not hasattr(fz, "lookahead")
+    mark("fused state"); x, P = fz.state(); assert x.shape == (32, 16) and P.shape == (32, 9, 9)
+    mark("fused report"); fz.report()
+    mark("fused health"); fz.health(return_summary=True)
+    mark("fused nees"); fz.nees(T("x_true_g", (32, 16), "float64"), blocks="r+v")
+    # the host-array forms, on a BatchedRelativePoseEKF that was never created
+    h = object.__new__(qla.BatchedRelativePoseEKF)
+    h.batch, h.dtype, h.device, h.params, h.derived, h._sequences = 128, _lib.QLE_F64, 0, ekf2.params, types.SimpleNamespace(num_states=9), []
+    h._h = C.c_void_p(ekf2._h)
+    try:
+        mark("host lookahead"); x, P, tk = h.lookahead(np.zeros((128, 6)), 8); assert x.shape == (128, 16) and tk is None
+        mark("host lookahead coast"); assert h.lookahead(np.zeros((128, 6)), 8, mask=np.ones(128), sigma_r_max=2.0)[2].shape == (128,)
+        mark("host fuse_banks"); x, P, w, best = h.fuse_banks(4, np.zeros(128)); assert P.shape == (32, 9, 9) and best.shape == (32,)
+        mark("host fuse_banks mask"); h.fuse_banks(8, np.zeros(128), np.ones(128))
+    finally:
+        h._h = C.c_void_p()   # nothing to destroy
+    mark("close"); seq.close(); bare.close(); io.close(); io2.close()
+    return rec.trace
+
+
+def side_libraries():
+    from quadrotor_landing_amd import _tensors
+    return {"devio": _tensors.DEVIO, "gate": gate.GATE, "consistency": consistency.CONSISTENCY, "health": health.HEALTH,
+            "lookahead": lookahead.LOOKAHEAD, "sequence": sequence.SEQUENCE, "score": score.SCORE, "bank": bank.BANK}
+
+
+def install(monkeypatch, rec):
+    """Recording stubs in place of the tick library and the eight side libraries; the one allocation function hands out fake tensors."""
+    from quadrotor_landing_amd import _tensors
+    monkeypatch.setattr(_lib, "_lib", Stub(rec, "ekf"))
+    for name, side in side_libraries().items():
+        monkeypatch.setattr(side, "_handle", Stub(rec, name))
+    monkeypatch.setattr(_tensors, "empty", lambda device, shape, dn, zero=False: rec.alloc(shape, dn, zero))
+    monkeypatch.setattr(_tensors, "current_stream", lambda device, *tensors: STREAM)
+
+
+def dump(trace, path):
+    with open(path, "w") as fh:
+        fh.write("[\n" + ",\n".join(json.dumps(c) for c in trace) + "\n]\n")
+
+
+def test_every_public_call_makes_the_native_calls_of_the_recorded_trace(monkeypatch):
+    rec = Recorder()
+    install(monkeypatch, rec)
+    got = json.loads(json.dumps(drive(rec)))
+    want = json.load(open(GOLDEN))
+    assert len(side_libraries()) == 8 and {c[0] for c in want} == set(side_libraries()) | {"ekf", "handle", "--"}
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, f"call {i}: made {g}, recorded {w}"
+    assert len(got) == len(want)

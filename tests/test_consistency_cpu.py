@@ -24,6 +24,7 @@ import consistency_util as cu
 import test_variant_table_cpu as tv
 from quadrotor_landing_amd import _lib, consistency, devio, gate
 from test_devio_cpu import FakeTensor, _kernels
+from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
@@ -167,13 +168,10 @@ class FakeEkf:
 
 
 def test_deviceio_refuses_bad_nees_arguments_before_any_gpu_call(monkeypatch):
-    def boom(*a, **k):
-        raise AssertionError("a native library was reached")
-    monkeypatch.setattr(devio, "devio_lib", boom)
-    monkeypatch.setattr(devio, "lib", boom)
-    monkeypatch.setattr(consistency, "consistency_lib", boom)
+    ekf, ekf9 = FakeEkf(), FakeEkf(num_states=9, est_bias=0)   # their parameters come from the tick library: made first
+    forbid_native(monkeypatch)
     B = 100
-    io = devio.DeviceIO(FakeEkf())
+    io = devio.DeviceIO(ekf)
     xt = FakeTensor((B, 16))
     bad = [
         dict(x_true=np.zeros((B, 16))),                               # a host array
@@ -195,7 +193,7 @@ def test_deviceio_refuses_bad_nees_arguments_before_any_gpu_call(monkeypatch):
     for kw in bad:
         with pytest.raises(ValueError):
             io.nees(**kw)
-    nine = devio.DeviceIO(FakeEkf(num_states=9, est_bias=0))
+    nine = devio.DeviceIO(ekf9)
     for blocks in ("ab", "r+wb", 8, 31):
         with pytest.raises(ValueError, match="bias block"):
             nine.nees(xt, blocks=blocks)

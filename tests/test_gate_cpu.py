@@ -32,7 +32,7 @@ from oracle import ekf_np
 from quadrotor_landing_amd import _lib, devio, gate
 from test_devio_cpu import FakeTensor, _kernels
 from test_innovation_cpu import CHI2_6_099
-from util import meas_near, rand_imu, rand_states
+from util import forbid_native, meas_near, rand_imu, rand_states
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
@@ -239,13 +239,10 @@ class FakeEkf:
 
 
 def test_deviceio_refuses_bad_gate_arguments_before_any_gpu_call(monkeypatch):
-    def boom(*a, **k):
-        raise AssertionError("a native library was reached")
-    monkeypatch.setattr(devio, "devio_lib", boom)
-    monkeypatch.setattr(devio, "lib", boom)
-    monkeypatch.setattr(gate, "gate_lib", boom)
+    ekf, ekf_mr = FakeEkf(), FakeEkf(multirate_ekf=1)   # their parameters come from the tick library: made first
+    forbid_native(monkeypatch)
     B = 100
-    io = devio.DeviceIO(FakeEkf())
+    io = devio.DeviceIO(ekf)
     u, z = FakeTensor((B, 6)), FakeTensor((B, 7))
     bad = [
         dict(u=u, chi2_max=16.81),                                   # a tick without tag poses
@@ -264,7 +261,7 @@ def test_deviceio_refuses_bad_gate_arguments_before_any_gpu_call(monkeypatch):
                dict(z=FakeTensor((B, 7), ptr=0x7F0000000008)), dict(z=np.zeros((B, 7)))):
         with pytest.raises(ValueError):
             io.innovation(**kw)
-    mr = devio.DeviceIO(FakeEkf(multirate_ekf=1))
+    mr = devio.DeviceIO(ekf_mr)
     for call in (lambda: mr.tick(u, z, chi2_max=16.81), lambda: mr.innovation(z)):
         with pytest.raises(_lib.QleError) as e:
             call()

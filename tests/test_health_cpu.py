@@ -19,6 +19,7 @@ import health_util as hu
 import test_variant_table_cpu as tv
 from quadrotor_landing_amd import _lib, consistency, devio, gate, health
 from test_devio_cpu import FakeTensor, _kernels, _needed
+from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
@@ -182,11 +183,7 @@ class FakeEkf:
 
 
 def test_deviceio_refuses_bad_lifecycle_arguments_before_any_gpu_call(monkeypatch):
-    def boom(*a, **k):
-        raise AssertionError("a native library was reached")
-    monkeypatch.setattr(devio, "devio_lib", boom)
-    monkeypatch.setattr(devio, "lib", boom)
-    monkeypatch.setattr(health, "health_lib", boom)
+    forbid_native(monkeypatch)
     B = 100
     io = devio.DeviceIO(FakeEkf())
     z, m = FakeTensor((B, 7)), FakeTensor((B,), dtype="uint8")

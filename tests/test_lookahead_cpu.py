@@ -23,6 +23,7 @@ import lookahead_util as lu
 import test_variant_table_cpu as tv
 from quadrotor_landing_amd import _lib, consistency, devio, gate, health, lookahead
 from test_devio_cpu import FakeTensor, _kernels, _needed
+from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
@@ -200,13 +201,10 @@ class FakeEkf:
 
 
 def test_deviceio_refuses_bad_lookahead_arguments_before_any_gpu_call(monkeypatch):
-    def boom(*a, **k):
-        raise AssertionError("a native library was reached")
-    monkeypatch.setattr(devio, "devio_lib", boom)
-    monkeypatch.setattr(devio, "lib", boom)
-    monkeypatch.setattr(lookahead, "lookahead_lib", boom)
+    ekf = FakeEkf()   # its parameters come from the tick library: made first
+    forbid_native(monkeypatch)
     B = 100
-    io = devio.DeviceIO(FakeEkf())
+    io = devio.DeviceIO(ekf)
     u, m = FakeTensor((B, 6)), FakeTensor((B,), dtype="uint8")
     for bad_u in (np.zeros((B, 6)), FakeTensor((B, 7)), FakeTensor((B, 6), dtype="float16"), FakeTensor((B, 6), device="cuda:1"),
                   FakeTensor((B, 6), device="cpu"), FakeTensor((B, 6), contiguous=False), FakeTensor((B, 6), ptr=0x7F0000000008)):

@@ -14,6 +14,7 @@ import pytest
 
 import test_devio_cpu as td
 from quadrotor_landing_amd import _lib, devio, sequence
+from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
@@ -194,10 +195,7 @@ def _fake_seq(io, K, ticks):
 
 
 def test_sequence_and_run_refuse_before_any_gpu_call(monkeypatch):
-    def boom(*a, **k):
-        raise AssertionError("a native library was reached")
-    for mod, name in ((devio, "devio_lib"), (devio, "lib"), (sequence, "sequence_lib")):
-        monkeypatch.setattr(mod, name, boom)
+    boom = forbid_native(monkeypatch)
     monkeypatch.setattr(FakeEkf, "make_inputs", boom, raising=False)
     io = devio.DeviceIO(FakeEkf())
     B, K = 100, 40

@@ -11,6 +11,27 @@ import oracle
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+def forbid_native(monkeypatch):
+    """Make every native library unreachable, for the "refuses before any GPU call" tests: the side-library loader, `_lib.lib`, and
+    every name a module of the package binds either under (`<x>_lib`, `lib`).  Whatever reaches one raises AssertionError; returns the function that
+    raises it, for what else counts as native in a test (a fake handle's `make_inputs`)."""
+    import sys
+
+    from quadrotor_landing_amd import _lib
+
+    def boom(*a, **k):
+        raise AssertionError("a native library was reached")
+    loader, tick = _lib.SideLibrary.load, _lib.lib
+    for name, mod in list(sys.modules.items()):
+        if mod is None or not name.startswith("quadrotor_landing_amd"):
+            continue
+        for attr, v in list(vars(mod).items()):
+            if v is tick or (getattr(v, "__func__", None) is loader and isinstance(getattr(v, "__self__", None), _lib.SideLibrary)):
+                monkeypatch.setattr(mod, attr, boom)
+    monkeypatch.setattr(_lib.SideLibrary, "load", boom)
+    return boom
+
+
 def param_sets():
     return json.load(open(os.path.join(GOLDEN, "param_sets.json")))
 
