@@ -9,6 +9,7 @@ from . import replay  # noqa: F401
 from . import bank  # noqa: F401
 from . import consistency  # noqa: F401
 from . import health  # noqa: F401
+from . import imm  # noqa: F401
 from . import lookahead  # noqa: F401
 from . import score  # noqa: F401
 from . import sequence  # noqa: F401

@@ -38,15 +38,22 @@ Filter banks (bank.py, libqle_bank.so): `bank(M)` reads the handle as B / M bank
 a `Fused` -- the members' posterior weights and every bank's moment-matched estimate, computed in one read-only launch into a workspace
 of its own and readable through the same calls (`state`, `report`, `health`, `nees`).
 
+Interacting multiple models (imm.py, libqle_imm.so): `imm(M, Pi)` returns an `Imm` over the same banks -- a Markov transition between the
+modes with recursive mode probabilities `logmu`, and the mixing step that re-initialises every member from the moment-matched mixture of
+its bank, in place, in one launch; `Imm.step(u, z, mask)` runs the cycle mix, score, tick, update around one tick and `Imm.fuse()` is
+`bank(M).fuse(logmu)`.
+
 Still host-fed through `BatchedRelativePoseEKF`: `set_state` and the per-filter stamps of `dynamic_meas_delay`
 (`filter_update(t_curr=..., apriltag_time=...)`).
 """
 import ctypes as C
+import math
 
 from . import _tensors as _t
 from . import bank as _bank
 from . import gate as _gate
 from . import health as _health
+from . import imm as _imm
 from . import lookahead as _look
 from . import score as _score
 from . import sequence as _seqm
@@ -261,6 +268,16 @@ class DeviceIO(DeviceRecords):
         every bank's moment-matched mixture, ONE read-only launch of k_bank_fuse per call.  logw: a float64 device tensor [B], or a
         `score.Scorer` (its log-likelihood).  The handle is not written; multirate handles included."""
         return _bank.Bank(self, members)
+
+    # ---- interacting multiple models: mixing and mode probabilities over the banks
+    def imm(self, members, Pi, logmu0=None, logmu_min=math.log(1e-12)):
+        """The handle's banks of `members` consecutive filters as an IMM estimator: an `imm.Imm` with the transition matrix Pi [M,M]
+        (a nested list, a numpy array or a tensor; checked on the host -- finite, >= 0, rows that add to 1 within 1e-12 -- and uploaded
+        once as float64), the log mode probabilities logmu0 [B] (None: uniform) and the floor logmu_min of the recursion (-inf: none).
+        `mix(mask)` re-initialises every member from its bank's mixture in ONE launch of k_imm_mix, in place; `update(loglik, mask)` is
+        the recursion in ONE launch of k_imm_update; `step(u, z, mask)` runs mix, score, tick, update around one tick; `fuse(mask)` is
+        `bank(members).fuse(logmu, mask)`; `mu()` the normalised probabilities.  Refused with multirate_ekf."""
+        return _imm.Imm(self, members, Pi, logmu0, logmu_min)
 
     def close(self):
         if self._seq is not None:

@@ -414,6 +414,14 @@ class BatchedRelativePoseEKF:
         x, P = ViewRecords(self, G, fused, workspace).state(dtype="float64")
         return x.cpu().numpy(), P.cpu().numpy(), w, best
 
+    def mix_banks(self, members, logmu, Pi, mask=None):
+        """The IMM mixing step of the handle's banks of `members` consecutive filters (`DeviceIO.imm`, `imm.Imm.mix`) with host arrays:
+        logmu [B] float64 (unnormalised log mode probabilities), Pi [M,M] (Pi[i][j] = P(mode i -> mode j); checked on the host), mask
+        [B] or None (all).  Every mixed member's record becomes the moment-matched mixture of its bank under mu_{i|j}, in place (one
+        launch of k_imm_mix).  Returns (logc [B] float64, mixed [B] uint8).  Refused with multirate_ekf."""
+        from . import imm as _imm
+        return _imm.mix_host(self, members, logmu, Pi, mask)
+
     # ---- reporting / control
     def report(self):
         """What the node publishes after a tick (relative_pose_EKF_node.cpp:192-220)."""
