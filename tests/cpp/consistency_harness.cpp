@@ -7,19 +7,18 @@
 // out (doubles): per filter nees, pd, err[15]
 // A compact run is handed NaN in every covariance word a compact record does not hold: they must not matter.
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
 
 #include "../../quadrotor_landing_amd/csrc/ekf_consistency.hpp"
+#include "harness_io.hpp"
 
 using namespace qle;
 
 static const int kHdr = 4, kPer = 16 + 225 + 16 + 6, kOut = 2 + 15;
 
 template <typename T, bool COMPACT>
-static void run(const double* h, const double* d, int64_t B, double* out)
+static void run(const double* h, const double* d, double* out)
 {
+    const int64_t B = (int64_t)h[0];
     const uint32_t blocks = (uint32_t)h[3];
     for (int64_t i = 0; i < B; ++i) {
         const double* f = d + i * kPer;
@@ -39,23 +38,7 @@ static void run(const double* h, const double* d, int64_t B, double* out)
 
 int main(int argc, char** argv)
 {
-    if (argc != 3) return 2;
-    FILE* fi = std::fopen(argv[1], "rb");
-    if (!fi) return 3;
-    std::vector<double> h(kHdr);
-    if (std::fread(h.data(), sizeof(double), kHdr, fi) != (size_t)kHdr) return 4;
-    const int64_t B = (int64_t)h[0];
-    std::vector<double> d((size_t)B * kPer), out((size_t)B * kOut);
-    if (std::fread(d.data(), sizeof(double), d.size(), fi) != d.size()) return 5;
-    std::fclose(fi);
-    const bool f64 = h[1] != 0, compact = h[2] != 0;
-    if (f64 && compact) run<double, true>(h.data(), d.data(), B, out.data());
-    else if (f64) run<double, false>(h.data(), d.data(), B, out.data());
-    else if (compact) run<float, true>(h.data(), d.data(), B, out.data());
-    else run<float, false>(h.data(), d.data(), B, out.data());
-    FILE* fo = std::fopen(argv[2], "wb");
-    if (!fo || std::fwrite(out.data(), sizeof(double), out.size(), fo) != out.size()) return 6;
-    std::fclose(fo);
-    std::printf("%lld\n", (long long)B);
-    return 0;
+    return harness_main(argc, argv, kHdr, no_check, per_filter(kPer), per_filter(kOut), [](const double* h, const double* d, double* out) {
+        by_dtype(h[1] != 0, [&](auto t) { by_flags(h[2] != 0, [&](auto compact) { run<decltype(t), decltype(compact)::value>(h, d, out); }); });
+    });
 }

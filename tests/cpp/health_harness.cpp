@@ -7,19 +7,18 @@
 // out (doubles): per filter status (what the kernel stores: 0 for a filter without state), no_state
 // A compact run is handed NaN in every covariance word a compact record does not hold: they must not matter.
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
 
 #include "../../quadrotor_landing_amd/csrc/ekf_health.hpp"
+#include "harness_io.hpp"
 
 using namespace qle;
 
 static const int kHdr = 9, kPer = 16 + 225, kOut = 2;
 
 template <typename T, bool COMPACT, int N>
-static void run(const double* h, const double* d, int64_t B, double* out)
+static void run(const double* h, const double* d, double* out)
 {
+    const int64_t B = (int64_t)h[0];
     HealthLimits lim;
     lim.r2 = h[4] * h[4]; lim.v2 = h[5] * h[5]; lim.th2 = h[6] * h[6];
     lim.qnorm_tol = h[7];
@@ -39,31 +38,16 @@ static void run(const double* h, const double* d, int64_t B, double* out)
 
 int main(int argc, char** argv)
 {
-    if (argc != 3) return 2;
-    FILE* fi = std::fopen(argv[1], "rb");
-    if (!fi) return 3;
-    std::vector<double> h(kHdr);
-    if (std::fread(h.data(), sizeof(double), kHdr, fi) != (size_t)kHdr) return 4;
-    const int64_t B = (int64_t)h[0];
-    std::vector<double> d((size_t)B * kPer), out((size_t)B * kOut);
-    if (std::fread(d.data(), sizeof(double), d.size(), fi) != d.size()) return 5;
-    std::fclose(fi);
-    const bool f64 = h[1] != 0, compact = h[2] != 0;
-    const int n = (int)h[3];
-    if (n != 15 && n != 9) return 7;
-    if (compact && n != 9) return 8;
-    if (f64) {
-        if (compact) run<double, true, 9>(h.data(), d.data(), B, out.data());
-        else if (n == 9) run<double, false, 9>(h.data(), d.data(), B, out.data());
-        else run<double, false, 15>(h.data(), d.data(), B, out.data());
-    } else {
-        if (compact) run<float, true, 9>(h.data(), d.data(), B, out.data());
-        else if (n == 9) run<float, false, 9>(h.data(), d.data(), B, out.data());
-        else run<float, false, 15>(h.data(), d.data(), B, out.data());
-    }
-    FILE* fo = std::fopen(argv[2], "wb");
-    if (!fo || std::fwrite(out.data(), sizeof(double), out.size(), fo) != out.size()) return 6;
-    std::fclose(fo);
-    std::printf("%lld\n", (long long)B);
-    return 0;
+    const auto check = [](const double* h) {
+        const int n = (int)h[3];
+        return n != 15 && n != 9 ? 7 : h[2] != 0 && n != 9 ? 8 : 0;
+    };
+    return harness_main(argc, argv, kHdr, check, per_filter(kPer), per_filter(kOut), [](const double* h, const double* d, double* out) {
+        by_dtype(h[1] != 0, [&](auto t) {
+            by_flags(h[2] != 0, h[3] == 15, [&](auto compact, auto fifteen) {   // check(): a compact record has 9 states
+                constexpr bool c = decltype(compact)::value;
+                run<decltype(t), c, decltype(fifteen)::value && !c ? 15 : 9>(h, d, out);
+            });
+        });
+    });
 }

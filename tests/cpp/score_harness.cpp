@@ -7,31 +7,22 @@
 //                ab_static[3], wb_static[3], then per tick, per filter: x[16], P[15][15], u[6], z[7], pfp[24], on -- the state BEFORE the tick
 // out (doubles): per filter the accumulator record, 40 words (include/qle_score.h)
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
 
 #include "../../quadrotor_landing_amd/csrc/ekf_score.hpp"
+#include "harness_io.hpp"
 
 using namespace qle;
 
 static const int kHdr = 5 + 4 + 3 + 4 + 9 + 3 + 12 + 6 + 3 + 3, kPer = 16 + 225 + 6 + 7 + 24 + 1;
 
 template <typename T, bool DIRECT>
-static void run(const double* h, const double* data, int64_t B, int ticks, bool use_pfp, double* out)
+static void run(const double* h, const double* data, double* out)
 {
-    DevParams<T> p;
+    const int64_t B = (int64_t)h[0];
+    const int ticks = (int)h[2];
+    const bool use_pfp = h[3] != 0;
     const double* q = h + 5;
-    p.dT = (T)q[0]; p.dTw = (T)q[1]; p.bias_on = (T)q[2]; p.small_ang_tol = (T)q[3]; q += 4;
-    for (int k = 0; k < 3; ++k) p.g[k] = (T)*q++;
-    for (int k = 0; k < 4; ++k) p.q_vc[k] = (T)*q++;
-    for (int k = 0; k < 9; ++k) p.C_vc[k] = (T)*q++;
-    for (int k = 0; k < 3; ++k) p.r_v_cv[k] = (T)*q++;
-    for (int k = 0; k < 12; ++k) p.Q[k] = (T)*q++;
-    for (int k = 0; k < 6; ++k) p.R[k] = (T)*q++;
-    for (int k = 0; k < 3; ++k) p.ab_static[k] = (T)*q++;
-    for (int k = 0; k < 3; ++k) p.wb_static[k] = (T)*q++;
-    p.compact = 0;
+    const DevParams<T> p = decode_params<T>(q, 0);
     for (int64_t i = 0; i < B; ++i) {
         double a[kScoreLive] = {};
         for (int t = 0; t < ticks; ++t) {
@@ -42,11 +33,7 @@ static void run(const double* h, const double* data, int64_t B, int ticks, bool 
                 for (int c = r; c < 15; ++c) Po[sidx(r, c)] = pregate_needs(r, c) ? (T)(0.5 * (f[16 + r * 15 + c] + f[16 + c * 15 + r])) : (T)NAN;   // a word the kernel does not load must not matter
             for (int k = 0; k < 6; ++k) u[k] = (T)f[241 + k];
             for (int k = 0; k < 7; ++k) z[k] = (T)f[247 + k];
-            const double* pf = f + 254;
-            Noise<T> nz;
-            for (int k = 0; k < 12; ++k) nz.Q[k] = use_pfp ? (T)pf[k] : p.Q[k];
-            for (int k = 0; k < 3; ++k) { nz.ab_static[k] = use_pfp ? (T)pf[12 + k] : p.ab_static[k]; nz.wb_static[k] = use_pfp ? (T)pf[15 + k] : p.wb_static[k]; }
-            for (int k = 0; k < 6; ++k) nz.R[k] = use_pfp ? (T)pf[18 + k] : p.R[k];
+            const Noise<T> nz = noise_from(p, f + 254, use_pfp);
             bool pd;
             const T nis = pregate_eval_pivots<T, DIRECT, true>(p, nz, x, Po, u, z, nu, S, d, pd);
             score_accumulate<T>(a, f[278] != 0, nis, pd, nu, S, d);
@@ -56,32 +43,11 @@ static void run(const double* h, const double* data, int64_t B, int ticks, bool 
     }
 }
 
-template <typename T>
-static void run_t(const double* h, const double* d, int64_t B, double* out)
-{
-    const int ticks = (int)h[2];
-    const bool pfp = h[3] != 0;
-    if (h[1] != 0) run<T, true>(h, d, B, ticks, pfp, out);
-    else run<T, false>(h, d, B, ticks, pfp, out);
-}
-
 int main(int argc, char** argv)
 {
-    if (argc != 3) return 2;
-    FILE* fi = std::fopen(argv[1], "rb");
-    if (!fi) return 3;
-    std::vector<double> h(kHdr);
-    if (std::fread(h.data(), sizeof(double), kHdr, fi) != (size_t)kHdr) return 4;
-    const int64_t B = (int64_t)h[0], ticks = (int64_t)h[2];
-    if (B < 1 || ticks < 1) return 4;
-    std::vector<double> d((size_t)(B * ticks) * kPer), out((size_t)B * kScoreWords);
-    if (std::fread(d.data(), sizeof(double), d.size(), fi) != d.size()) return 5;
-    std::fclose(fi);
-    if (h[4] != 0) run_t<double>(h.data(), d.data(), B, out.data());
-    else run_t<float>(h.data(), d.data(), B, out.data());
-    FILE* fo = std::fopen(argv[2], "wb");
-    if (!fo || std::fwrite(out.data(), sizeof(double), out.size(), fo) != out.size()) return 6;
-    std::fclose(fo);
-    std::printf("%lld\n", (long long)B);
-    return 0;
+    const auto check = [](const double* h) { return h[0] < 1 || h[2] < 1 ? 4 : 0; };
+    return harness_main(argc, argv, kHdr, check, [](const double* h) { return (size_t)((int64_t)h[0] * (int64_t)h[2]) * kPer; }, per_filter(kScoreWords),
+                        [](const double* h, const double* d, double* out) {
+                            by_dtype(h[4] != 0, [&](auto t) { by_flags(h[1] != 0, [&](auto direct) { run<decltype(t), decltype(direct)::value>(h, d, out); }); });
+                        });
 }

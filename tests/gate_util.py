@@ -1,14 +1,16 @@
 """Shared by test_gate_cpu.py and test_gpu_gate.py: the reference of the gate in front of the fused tick -- the dense oracle's
-prediction_step followed by the numpy restatement of the innovation (test_innovation_cpu.innovation_ref) -- and the displaced tag
+prediction_step followed by the numpy restatement of the innovation (innovation_util.innovation_ref) -- and the displaced tag
 poses of the rejection case."""
 import numpy as np
 
 import oracle
-from test_innovation_cpu import CHI2_6_099, innovation_ref_batch
+from innovation_util import CHI2_6_099, innovation_ref_batch
 from util import meas_near, qmul
 
 # tolerances against the fp64 reference, relative to the largest element of each output (NIS: to itself): the project's own for the
 # innovation diagnostics (test_gpu_innovation.py); the predict step in front adds 5e-7 in fp32 (tests/tolerances.md), well inside
+HW = dict(r_v_cv=[0.06036412, -0.00145196, -0.04439579], q_vc=[-0.7035177, 0.7106742, 0.0014521, -0.0017207],
+          ab_static=[0.2, -0.09, -0.03], wb_static=[-0.02, -0.01, 0.003])
 TOL = {"f64": dict(nu=1e-12, S=1e-12, nis=1e-12), "f32": dict(nu=3e-5, S=3e-5, nis=1e-4)}
 
 

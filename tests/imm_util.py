@@ -146,3 +146,29 @@ def deviations(logc, xm, Pm, ref):
     sP = ref.sP[live].reshape(-1, nb, 3, nb, 3).sum(axis=(2, 4))
     out["P"] = bu._rel(dP, sP)
     return out
+
+
+def update_case(rng, M, G):
+    """(logc, loglik, mask) with the members the recursion treats specially: per bank a loglik of -inf, a NaN one, a masked member and
+    a logc of -inf (M >= 8: all four; M = 2: one in turn), loglik otherwise spread over tens of nats; the last bank has no member left."""
+    B = M * G
+    logc = np.log(rng.dirichlet(np.ones(M), size=G)).reshape(B)
+    loglik = rng.uniform(-40.0, 5.0, size=B)
+    mask = np.ones(B, np.uint8)
+    for g in range(G - 1):
+        lanes = rng.permutation(M)[:4] if M >= 8 else [int(rng.integers(M))] * 4
+        for kind, l in enumerate(lanes):
+            if M < 8 and kind != g % 5:
+                continue
+            i = g * M + int(l)
+            if kind == 0:
+                loglik[i] = -np.inf
+            elif kind == 1:
+                loglik[i] = np.nan
+            elif kind == 2:
+                mask[i] = 0
+            else:
+                logc[i] = -np.inf
+    mask[-M::2] = 0
+    logc[-M + 1::2] = -np.inf
+    return logc, loglik, mask

@@ -12,44 +12,35 @@ Measured deviations of the host-compiled arithmetic from the truth (printed per 
 tests/tolerances_bank.md.
 """
 import ctypes as C
+import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import bank_util as bu
-import test_variant_table_cpu as tv
+import host_harness
+import side_lib_util
+from elf_util import _kernels, _needed
 from quadrotor_landing_amd import _lib, bank, devio
-from test_devio_cpu import FakeTensor, _kernels, _needed
+from side_lib_util import FakeTensor, assert_audit_counts, assert_exports_and_binds, ensure_built, kernel_descriptors, run_audit, scratch_free
 from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "qle_bank.h")
 N_KERNELS = 4   # k_bank_fuse: T x COMPACT
 
 
 @pytest.fixture(scope="module")
 def bank_so():
-    if not os.path.exists(bank.BANK_LIB_PATH):
-        subprocess.run(["make", "-C", CSRC, "../libqle_bank.so"], check=True)
-    return bank.BANK_LIB_PATH
+    return ensure_built("bank")
 
 
 # ---------------------------------------------------------------- 1. header, exports, kernels, audit, resources
 def test_library_exports_and_binds_every_declared_function(bank_so):
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(qbk_[a-z0-9_]+)\s*\(", txt)))
-    assert names == ["qbk_fuse", "qbk_fuse_host", "qbk_last_error", "qbk_launch_count", "qbk_workspace_bytes"]
-    L = bank.bank_lib()
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/qle_bank.h but not exported"
-    assert sorted(bank.SYMBOLS) == names
-    d = open(bank_so, "rb").read()
-    exported = {s for s in tv._symbols(d, 11) if s.startswith("qbk_")}   # SHT_DYNSYM
-    assert exported == set(names), sorted(exported ^ set(names))
+    _, txt = assert_exports_and_binds(bank, HEADER, "qbk", bank_so,
+                                      ["qbk_fuse", "qbk_fuse_host", "qbk_last_error", "qbk_launch_count", "qbk_workspace_bytes"])
     assert int(re.search(r"#define QBK_MAX_MEMBERS (\d+)", txt).group(1)) == bank.MAX_MEMBERS == 64
 
 
@@ -72,15 +63,11 @@ def test_library_links_the_hip_runtime_only(bank_so):
 
 @pytest.fixture(scope="module")
 def audit(bank_so):
-    r = subprocess.run(["make", "-C", CSRC, "audit-bank"], capture_output=True, text=True, timeout=900)
-    return r, os.path.join(CSRC, "build", "asm", "bank_capi.s")
+    return run_audit("bank")
 
 
 def test_generated_device_code_passes_the_stale_exec_audit(audit):
-    r, _ = audit
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    m = re.search(r"audit-bank: no register copy under a stale EXEC in (\d+) kernels", r.stdout)
-    assert m and int(m.group(1)) == N_KERNELS, r.stdout[-2000:]
+    assert_audit_counts(audit[0], "bank", N_KERNELS)
 
 
 def test_no_kernel_uses_scratch_memory_or_lds(audit):
@@ -88,29 +75,18 @@ def test_no_kernel_uses_scratch_memory_or_lds(audit):
     leaves room for at least two waves per SIMD (P is streamed: nowhere near the 240 registers of a resident fp64 covariance)."""
     r, asm = audit
     assert r.returncode == 0
-    txt = open(asm).read()
-    found = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, flags=re.S):
-        name = _lib.demangle(m.group(1))
-        scratch = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", m.group(2)).group(1))
-        lds = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", m.group(2)).group(1))
-        vgpr = int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", m.group(2)).group(1))
-        found[name] = (scratch, lds, vgpr)
+    found, meta = kernel_descriptors(asm)
     assert len(found) == N_KERNELS and all("k_bank_fuse<" in k for k in found), sorted(found)
     for name, (scratch, lds, vgpr) in found.items():
         print(f"{name.split('(')[0]}: scratch {scratch} B, LDS {lds} B, registers {vgpr}")
         assert scratch == 0, (name, scratch)
         assert lds == 0, (name, lds)
         assert vgpr <= 256, (name, vgpr)
-    assert all(re.search(r"\.private_segment_fixed_size:\s+0\b", s) for s in re.findall(r"\.private_segment_fixed_size:.*", txt))
+    assert scratch_free(meta), meta
 
 
 # ---------------------------------------------------------------- 2. refusals, before any GPU call
-def _view(batch=128, dtype=_lib.QLE_F32, n=15, compact=0):
-    v = _lib.QleDeviceView()
-    v.struct_size = C.sizeof(v); v.device = 0; v.dtype = dtype; v.num_states = n; v.batch = batch; v.padded_batch = -(-batch // 64) * 64
-    v.state = 0x7F0000000000; v.state_words = 144; v.record_words = 64 if compact else 136; v.compact = compact
-    return v
+_view = functools.partial(side_lib_util._view, batch=128)
 
 
 def test_library_refuses_before_any_gpu_call(bank_so):
@@ -224,35 +200,18 @@ def test_truth_is_the_mixture_covariance_where_members_share_a_quaternion(M, n):
 
 
 # ---------------------------------------------------------------- 4. the arithmetic on the host, once more under the sanitizers
-SRC = os.path.join(ROOT, "tests", "cpp", "bank_harness.cpp")
-GXX = ["g++", "-std=c++17", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-       "-Wno-maybe-uninitialized", "-Wno-unused-but-set-variable"]
-
-
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
     """tests/cpp/bank_harness.cpp: the arithmetic of ekf_bank.hpp compiled by g++ (the HIP headers define the device decorators away),
     once as it is and once as a stand-alone program under AddressSanitizer and UBSan."""
-    d = tmp_path_factory.mktemp("bk")
-    plain, san = str(d / "bank_harness"), str(d / "bank_harness_san")
-    subprocess.run(GXX + ["-O2", "-o", plain, SRC], check=True)
-    subprocess.run(GXX + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", san, SRC], check=True)
-    return plain, san
+    return host_harness.build("bank_harness", tmp_path_factory)
 
 
 def run_harness(exe, tmp, dtype, compact, M, x, P, logw, mask):
     B, n = x.shape[0], P.shape[1]
     G = B // M
-    P15 = np.full((B, 15, 15), np.nan if compact else 0.0); P15[:, :n, :n] = P   # compact: the words outside the pose block do not exist
-    if n == 9 and not compact:
-        P15[:, 9:, :] = 0.0; P15[:, :, 9:] = 0.0
-    per = np.concatenate([x, P15.reshape(B, 225), logw[:, None], mask[:, None].astype(np.float64)], axis=1)
-    fin, fout = str(tmp / "in.bin"), str(tmp / "out.bin")
-    with open(fin, "wb") as fh:
-        np.asarray([B, int(dtype == "f64"), int(compact), M], np.float64).tofile(fh); np.ascontiguousarray(per, np.float64).tofile(fh)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "" and int(r.stdout) == B, (r.returncode, r.stdout, r.stderr[-3000:])
-    o = np.fromfile(fout, np.float64)
+    per = np.concatenate([x, host_harness.full_P(P, compact), logw[:, None], mask[:, None].astype(np.float64)], axis=1)
+    o = host_harness.run(exe, tmp, [B, int(dtype == "f64"), int(compact), M], [per], -1)
     w, bank_out = o[:B], o[B:].reshape(G, 242)
     Pf = bank_out[:, 17:].reshape(G, 15, 15)
     assert not Pf[:, n:, :].any() and not Pf[:, :, n:].any()

@@ -13,7 +13,7 @@ import numpy as np
 
 import quadrotor_landing_amd as qla
 from quadrotor_landing_amd import _lib, bank, consistency, devio, gate, health, lookahead, score, sequence
-from test_devio_cpu import FakeTensor
+from side_lib_util import FakeTensor
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "boundary_trace.json")
 STREAM = 0x5000         # the caller's current stream

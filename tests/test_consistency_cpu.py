@@ -15,42 +15,29 @@ Measured worst deviation / tolerance of the host-compiled arithmetic (B = 300 pe
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import consistency_util as cu
-import test_variant_table_cpu as tv
+import host_harness
+from elf_util import _kernels
 from quadrotor_landing_amd import _lib, consistency, devio, gate
-from test_devio_cpu import FakeTensor, _kernels
+from side_lib_util import FakeTensor, _params, _view, assert_audit_counts, assert_exports_and_binds, ensure_built, kernel_descriptors, run_audit, scratch_free
 from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "qle_consistency.h")
 AB_STATIC, WB_STATIC = np.array([0.2, -0.09, -0.03]), np.array([-0.02, -0.01, 0.003])
 
 
 @pytest.fixture(scope="module")
 def cons_so():
-    if not os.path.exists(consistency.CONSISTENCY_LIB_PATH):
-        subprocess.run(["make", "-C", CSRC, "../libqle_consistency.so"], check=True)
-    return consistency.CONSISTENCY_LIB_PATH
+    return ensure_built("consistency")
 
 
 def test_library_exports_and_binds_every_declared_function(cons_so):
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(qcs_[a-z0-9_]+)\s*\(", txt)))
-    assert names == ["qcs_last_error", "qcs_launch_count", "qcs_nees", "qcs_nees_host"]
-    L = consistency.consistency_lib()
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/qle_consistency.h but not exported"
-    assert sorted(consistency.SYMBOLS) == names
-    # and nothing else with the library's prefix is exported
-    d = open(cons_so, "rb").read()
-    exported = {s for s in tv._symbols(d, 11) if s.startswith("qcs_")}   # SHT_DYNSYM
-    assert exported == set(names), sorted(exported ^ set(names))
+    assert_exports_and_binds(consistency, HEADER, "qcs", cons_so, ["qcs_last_error", "qcs_launch_count", "qcs_nees", "qcs_nees_host"])
 
 
 def test_summary_struct_is_eight_doubles_in_the_header_order():
@@ -74,15 +61,11 @@ def test_kernels_are_disjoint_from_the_three_existing_libraries(cons_so):
 
 @pytest.fixture(scope="module")
 def audit(cons_so):
-    r = subprocess.run(["make", "-C", CSRC, "audit-consistency"], capture_output=True, text=True, timeout=900)
-    return r, os.path.join(CSRC, "build", "asm", "consistency_capi.s")
+    return run_audit("consistency")
 
 
 def test_generated_device_code_passes_the_stale_exec_audit(audit):
-    r, _ = audit
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    m = re.search(r"audit-consistency: no register copy under a stale EXEC in (\d+) kernels", r.stdout)
-    assert m and int(m.group(1)) == 9, r.stdout[-2000:]
+    assert_audit_counts(audit[0], "consistency", 9)
 
 
 def test_no_kernel_uses_scratch_memory(audit):
@@ -90,38 +73,17 @@ def test_no_kernel_uses_scratch_memory(audit):
     the register counts the launch bounds promise -- fp32 within the 256 registers that leave room for two waves per SIMD."""
     r, asm = audit
     assert r.returncode == 0
-    txt = open(asm).read()
-    found = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, flags=re.S):
-        name = _lib.demangle(m.group(1))
-        scratch = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", m.group(2)).group(1))
-        vgpr = int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", m.group(2)).group(1))
-        found[name] = (scratch, vgpr)
+    found, meta = kernel_descriptors(asm)
     nees = {k: v for k, v in found.items() if "k_nees<" in k}
     assert len(nees) == 8 and len(found) == 9, sorted(found)
-    for name, (scratch, vgpr) in found.items():
+    for name, (scratch, _, vgpr) in found.items():
         print(f"{name.split('(')[0]}: scratch {scratch} B, registers {vgpr}")
         assert scratch == 0, (name, scratch)
         assert vgpr <= (256 if "k_nees<float" in name else 512), (name, vgpr)
-    assert all(re.search(r"\.private_segment_fixed_size:\s+0\b", s) for s in re.findall(r"\.private_segment_fixed_size:.*", txt))
+    assert scratch_free(meta), meta
 
 
 # ---------------------------------------------------------------- refusals, before any GPU call
-def _view(batch=100, dtype=_lib.QLE_F32, n=15):
-    v = _lib.QleDeviceView()
-    v.struct_size = C.sizeof(v); v.device = 0; v.dtype = dtype; v.num_states = n; v.batch = batch; v.padded_batch = -(-batch // 64) * 64
-    v.state = 0x7F0000000000; v.state_words = 144; v.record_words = 136
-    return v
-
-
-def _params(**kw):
-    p = _lib.QleParams()
-    _lib.check(_lib.lib().qle_params_default(C.byref(p)))
-    for k, val in kw.items():
-        setattr(p, k, val)
-    return p
-
-
 def test_library_refuses_before_any_gpu_call(cons_so):
     """No GPU here: a call that got as far as the HIP runtime would return QLE_ERR_HIP (or crash on the fake pointers), not these."""
     K = consistency.consistency_lib()
@@ -213,24 +175,15 @@ def test_block_names():
 # ---------------------------------------------------------------- the arithmetic on the host
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    """tests/cpp/consistency_harness.cpp: ekf_consistency.hpp's nees_eval compiled by g++ (the HIP headers define the device decorators away)."""
-    exe = str(tmp_path_factory.mktemp("cnh") / "consistency_harness")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-Wall", "-Wno-unknown-pragmas",
-                    "-Wno-unused-function", "-Wno-maybe-uninitialized", "-o", exe, os.path.join(ROOT, "tests", "cpp", "consistency_harness.cpp")],
-                   check=True)
-    return exe
+    """tests/cpp/consistency_harness.cpp: ekf_consistency.hpp's nees_eval compiled by g++ (the HIP headers define the device decorators away),
+    once as it is and once as a stand-alone program under AddressSanitizer and UBSan."""
+    return host_harness.build("consistency_harness", tmp_path_factory)
 
 
 def run_harness(exe, tmp, dtype, compact, blocks, x, P, xt, ab, wb):
     B, n = x.shape[0], P.shape[1]
-    P15 = np.zeros((B, 15, 15)); P15[:, :n, :n] = P
-    per = np.concatenate([x, P15.reshape(B, 225), xt, np.broadcast_to(ab, (B, 3)), np.broadcast_to(wb, (B, 3))], axis=1)
-    fin, fout = str(tmp / "in.bin"), str(tmp / "out.bin")
-    with open(fin, "wb") as fh:
-        np.asarray([B, int(dtype == "f64"), int(compact), blocks], np.float64).tofile(fh); np.ascontiguousarray(per, np.float64).tofile(fh)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0 and int(r.stdout) == B, (r.returncode, r.stdout, r.stderr)
-    o = np.fromfile(fout, np.float64).reshape(B, 17)
+    per = np.concatenate([x, host_harness.full_P(P), xt, np.broadcast_to(ab, (B, 3)), np.broadcast_to(wb, (B, 3))], axis=1)
+    o = host_harness.run(exe, tmp, [B, int(dtype == "f64"), int(compact), blocks], [per], (B, 17))
     return o[:, 0], o[:, 1] != 0, o[:, 2:2 + n]
 
 
@@ -261,13 +214,14 @@ def test_host_compiled_arithmetic_matches_the_dense_solve_on_every_marginal(harn
     assert ang[big].max() > 160.0 and (xt[neg, 9] < 0).all()
     worst_n = worst_e = 0.0
     for blocks in range(1, 32 if n == 15 else 8):
-        nees, pd, err = run_harness(harness, tmp_path, dtype, compact, blocks, x, P, xt, ab, wb)
         ref = cu.nees_ref(P, eref, blocks)
-        assert pd.all() and np.isfinite(nees).all()
-        rn, re_ = cu.nees_ratio(nees, ref, P, dtype), cu.err_ratio(err, eref, dtype)
-        worst_n, worst_e = max(worst_n, rn), max(worst_e, re_)
-        assert rn <= 1.0, (blocks, rn)       # every filter of every selection: nothing is left out
-        assert re_ <= 1.0, (blocks, re_)
+        for exe in harness:                  # the plain build, then the same file under ASan + UBSan
+            nees, pd, err = run_harness(exe, tmp_path, dtype, compact, blocks, x, P, xt, ab, wb)
+            assert pd.all() and np.isfinite(nees).all()
+            rn, re_ = cu.nees_ratio(nees, ref, P, dtype), cu.err_ratio(err, eref, dtype)
+            worst_n, worst_e = max(worst_n, rn), max(worst_e, re_)
+            assert rn <= 1.0, (blocks, rn)       # every filter of every selection: nothing is left out
+            assert re_ <= 1.0, (blocks, re_)
     print(f"{dtype} n={n} compact={compact}: worst |nees - ref| / tol {worst_n:.3g}, worst err deviation / bar {worst_e:.3g}")
 
 
@@ -276,9 +230,10 @@ def test_indefinite_covariance_gives_nan_and_is_flagged(harness, cases, tmp_path
     x, P, xt, ab, wb, eref = (a[:8].copy() for a in cases[dtype, 15])
     P0 = P.copy()
     P[3, 4, 4] = -P[3, 4, 4]     # a negative diagonal entry in the velocity block
-    nees, pd, _ = run_harness(harness, tmp_path, dtype, False, 31, x, P, xt, ab, wb)
-    assert np.isnan(nees[3]) and np.isfinite(np.delete(nees, 3)).all()
-    assert (~pd).sum() == 1 and not pd[3]                                  # n_not_pd = 1
-    # the marginal that leaves the bad block out is positive definite again
-    nees, pd, _ = run_harness(harness, tmp_path, dtype, False, 31 & ~2, x, P, xt, ab, wb)
-    assert pd.all() and cu.nees_ratio(nees, cu.nees_ref(P, eref, 29), P0, dtype) <= 1.0
+    for exe in harness:
+        nees, pd, _ = run_harness(exe, tmp_path, dtype, False, 31, x, P, xt, ab, wb)
+        assert np.isnan(nees[3]) and np.isfinite(np.delete(nees, 3)).all()
+        assert (~pd).sum() == 1 and not pd[3]                                  # n_not_pd = 1
+        # the marginal that leaves the bad block out is positive definite again
+        nees, pd, _ = run_harness(exe, tmp_path, dtype, False, 31 & ~2, x, P, xt, ab, wb)
+        assert pd.all() and cu.nees_ratio(nees, cu.nees_ref(P, eref, 29), P0, dtype) <= 1.0

@@ -5,20 +5,19 @@ the kernels' index arithmetic -- compiled for the host under ASan/UBSan -- agree
 published layout on every word of a ragged batch, and DeviceIO refuses bad tensors before any GPU call."""
 import ctypes as C
 import os
-import re
-import struct
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-import test_variant_table_cpu as tv
+import host_harness
+from elf_util import _kernels, _needed
 from quadrotor_landing_amd import _lib, devio
+from side_lib_util import FakeEkf, FakeTensor, _Reader, assert_audit_counts, assert_exports_and_binds, ensure_built, run_audit
 from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "qle_devio.h")
 CLANGXX = "/opt/rocm/lib/llvm/bin/clang++"
 B_RAGGED = 2391   # the variant table's ragged size: 37 whole tiles and one of 23 filters
@@ -26,20 +25,12 @@ B_RAGGED = 2391   # the variant table's ragged size: 37 whole tiles and one of 2
 
 @pytest.fixture(scope="module")
 def devio_so():
-    if not os.path.exists(devio.DEVIO_LIB_PATH):
-        subprocess.run(["make", "-C", CSRC, "../libqle_devio.so"], check=True)
-    return devio.DEVIO_LIB_PATH
+    return ensure_built("devio")
 
 
 def test_library_exports_and_binds_every_declared_function(devio_so):
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(qdv_[a-z0-9_]+)\s*\(", txt)))
+    names, _ = assert_exports_and_binds(devio, HEADER, "qdv", devio_so)
     assert len(names) >= 6
-    L = C.CDLL(devio_so)
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/qle_devio.h but not exported"
-    assert sorted(devio.SYMBOLS) == names
-    assert devio.devio_lib() is not None
 
 
 def test_view_struct_sizes_match_the_header(tmp_path):
@@ -56,18 +47,7 @@ def test_view_struct_sizes_match_the_header(tmp_path):
 
 
 def test_generated_device_code_passes_the_stale_exec_audit(devio_so):
-    r = subprocess.run(["make", "-C", CSRC, "audit-devio"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    m = re.search(r"audit-devio: no register copy under a stale EXEC in (\d+) kernels", r.stdout)
-    assert m and int(m.group(1)) >= 1, r.stdout[-2000:]
-
-
-def _kernels(path):
-    d = open(path, "rb").read()
-    kds = []
-    for co in tv._gfx950_code_objects(d):
-        kds += [s[:-3] for s in tv._symbols(co, 2) if s.endswith(".kd")]
-    return set(kds)
+    assert_audit_counts(run_audit("devio")[0], "devio")
 
 
 def test_kernels_are_disjoint_from_the_tick_library(devio_so):
@@ -80,21 +60,6 @@ def test_kernels_are_disjoint_from_the_tick_library(devio_so):
     # the three kernel families of the boundary, every dtype pair of each
     fam = {i.split("<")[0].split("::")[1] for i in ids}
     assert fam == {"k_dv_pack", "k_dv_state", "k_dv_report"}, fam
-
-
-def _needed(path):
-    d = open(path, "rb").read()
-    secs = tv._sections(d)
-    dyn = [s for s in secs if s[0] == ".dynamic"][0]
-    strtab = secs[dyn[6]][4]
-    out = []
-    for o in range(dyn[4], dyn[4] + dyn[5], 16):
-        tag, val = struct.unpack_from("<qQ", d, o)
-        if tag == 0:
-            break
-        if tag == 1:   # DT_NEEDED
-            out.append(d[strtab + val:d.index(b"\0", strtab + val)].decode())
-    return out
 
 
 def test_library_links_the_hip_runtime_only(devio_so):
@@ -141,27 +106,14 @@ def np_p_word(a, b, compact):
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
     """tests/cpp/devio_index_harness.cpp built for the host with ASan + UBSan and run on the ragged batch."""
-    d = tmp_path_factory.mktemp("dvh")
-    exe, out = str(d / "dvh"), str(d / "dvh.bin")
-    subprocess.run([CLANGXX, "-O1", "-g", "-std=c++17", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-Wall", "-Wno-unknown-pragmas",
-                    "-Wno-unused-function", "-Wno-unused-variable", "-Wno-pass-failed", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-o", exe, os.path.join(ROOT, "tests", "cpp", "devio_index_harness.cpp")], check=True)
+    exe, = host_harness.build("devio_index_harness", tmp_path_factory, plain=False, cxx=CLANGXX,
+                              flags=host_harness.FLAGS[:5] + ("-Wno-unused-variable", "-Wno-pass-failed"))
+    out = exe + ".bin"
     r = subprocess.run([exe, str(B_RAGGED), out], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]   # a sanitizer report ends the program with a non-zero status
     data = np.fromfile(out, dtype=np.int64)
     assert data.size == int(r.stdout.split()[0])
     return data
-
-
-class _Reader:
-    def __init__(self, a):
-        self.a, self.p = a, 0
-
-    def take(self, n):
-        v = self.a[self.p:self.p + n]
-        assert v.size == n
-        self.p += n
-        return v
 
 
 def test_index_arithmetic_agrees_with_the_published_layout(harness):
@@ -233,35 +185,6 @@ def test_index_arithmetic_agrees_with_the_published_layout(harness):
 
 
 # ---------------------------------------------------------------- DeviceIO argument checks (no GPU call is reached)
-class FakeTensor:
-    def __init__(self, shape, dtype="float32", device="cuda:0", contiguous=True, ptr=0x7F0000000000):
-        self.shape, self.dtype, self.device, self._c, self._p = tuple(shape), dtype, device, contiguous, ptr
-
-    def data_ptr(self):
-        return self._p
-
-    def is_contiguous(self):
-        return self._c
-
-    def numel(self):
-        return int(np.prod(self.shape, dtype=np.int64))
-
-    def __getitem__(self, idx):
-        """A view: ints drop a dimension, slices shorten it; the storage stays the base's."""
-        idx = idx if isinstance(idx, tuple) else (idx,)
-        idx += (slice(None),) * (len(self.shape) - len(idx))
-        shape = [len(range(*i.indices(d))) for d, i in zip(self.shape, idx) if isinstance(i, slice)]
-        return type(self)(shape, self.dtype, self.device, ptr=self._p)
-
-    def zero_(self):
-        return self
-
-
-class FakeEkf:
-    batch, dtype, device, num_states = 100, _lib.QLE_F32, 0, 15
-    _h = None
-
-
 def test_deviceio_refuses_bad_tensors_before_any_gpu_call(monkeypatch):
     forbid_native(monkeypatch)
     io = devio.DeviceIO(FakeEkf())

@@ -19,47 +19,33 @@ test_gpu_innovation.py records for k_innov, 1.06e-5, on its own seeds); the pred
 """
 import ctypes as C
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_harness
 import oracle
-import test_variant_table_cpu as tv
-from gate_util import TOL, clear_of_threshold, displaced_tag_poses, predict_then_innovation, rel
+import side_lib_util
+from elf_util import _kernels
+from gate_util import HW, TOL, clear_of_threshold, displaced_tag_poses, predict_then_innovation, rel
+from innovation_util import CHI2_6_099
 from oracle import ekf_np
 from quadrotor_landing_amd import _lib, devio, gate
-from test_devio_cpu import FakeTensor, _kernels
-from test_innovation_cpu import CHI2_6_099
+from side_lib_util import FakeTensor, _params, _views, assert_audit_counts, assert_exports_and_binds, ensure_built, run_audit
 from util import forbid_native, meas_near, rand_imu, rand_states
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "qle_gate.h")
-HW = dict(r_v_cv=[0.06036412, -0.00145196, -0.04439579], q_vc=[-0.7035177, 0.7106742, 0.0014521, -0.0017207],
-          ab_static=[0.2, -0.09, -0.03], wb_static=[-0.02, -0.01, 0.003])
 
 
 @pytest.fixture(scope="module")
 def gate_so():
-    if not os.path.exists(gate.GATE_LIB_PATH):
-        subprocess.run(["make", "-C", CSRC, "../libqle_gate.so"], check=True)
-    return gate.GATE_LIB_PATH
+    return ensure_built("gate")
 
 
 def test_library_exports_and_binds_every_declared_function(gate_so):
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(qgt_[a-z0-9_]+)\s*\(", txt)))
+    names, _ = assert_exports_and_binds(gate, HEADER, "qgt", gate_so)
     assert len(names) >= 3
-    L = gate.gate_lib()
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/qle_gate.h but not exported"
-    assert sorted(gate.SYMBOLS) == names
-    # and nothing else with the library's prefix is exported
-    d = open(gate_so, "rb").read()
-    exported = {s for s in tv._symbols(d, 11) if s.startswith("qgt_")}   # SHT_DYNSYM
-    assert exported == set(names), sorted(exported ^ set(names))
 
 
 def test_kernels_are_disjoint_from_the_tick_and_boundary_libraries(gate_so):
@@ -74,36 +60,22 @@ def test_kernels_are_disjoint_from_the_tick_and_boundary_libraries(gate_so):
 
 
 def test_generated_device_code_passes_the_stale_exec_audit(gate_so):
-    r = subprocess.run(["make", "-C", CSRC, "audit-gate"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    m = re.search(r"audit-gate: no register copy under a stale EXEC in (\d+) kernels", r.stdout)
-    assert m and int(m.group(1)) > 0, r.stdout[-2000:]
+    assert_audit_counts(run_audit("gate")[0], "gate")
 
 
 # ---------------------------------------------------------------- the arithmetic on the host
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    """tests/cpp/pregate_harness.cpp: ekf_pregate.hpp's pregate_eval compiled by g++ (the HIP headers define the device decorators away)."""
-    exe = str(tmp_path_factory.mktemp("pgh") / "pregate_harness")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-Wall", "-Wno-unknown-pragmas",
-                    "-Wno-unused-function", "-Wno-maybe-uninitialized", "-o", exe, os.path.join(ROOT, "tests", "cpp", "pregate_harness.cpp")],
-                   check=True)
-    return exe
+    """tests/cpp/pregate_harness.cpp: ekf_pregate.hpp's pregate_eval compiled by g++ (the HIP headers define the device decorators away),
+    once as it is and once as a stand-alone program under AddressSanitizer and UBSan."""
+    return host_harness.build("pregate_harness", tmp_path_factory)
 
 
 def run_harness(exe, tmp, po, dtype, predict, x, P, u, z, pfp):
-    B, n = x.shape[0], po.num_states
-    hdr = [B, po.direct_orien_method, int(predict), int(pfp is not None), int(dtype == "f64"),
-           po.dT_nom, po.dT_nom if po.est_bias else 0.0, float(po.est_bias), po.small_ang_tol,
-           *po.g, *po.q_vc, *po.C_vc, *po.r_v_cv, *po.Q, *po.R, *po.ab_static, *po.wb_static]
-    P15 = np.zeros((B, 15, 15)); P15[:, :n, :n] = P
-    per = np.concatenate([x, P15.reshape(B, 225), u, z, np.zeros((B, 24)) if pfp is None else pfp], axis=1)
-    fin, fout = str(tmp / "in.bin"), str(tmp / "out.bin")
-    with open(fin, "wb") as fh:
-        np.asarray(hdr, np.float64).tofile(fh); np.ascontiguousarray(per, np.float64).tofile(fh)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0 and int(r.stdout) == B, (r.returncode, r.stdout, r.stderr)
-    o = np.fromfile(fout, np.float64).reshape(B, 43)
+    B = x.shape[0]
+    hdr = [B, po.direct_orien_method, int(predict), int(pfp is not None), int(dtype == "f64"), *host_harness.params_header(po)]
+    per = np.concatenate([x, host_harness.full_P(P), u, z, np.zeros((B, 24)) if pfp is None else pfp], axis=1)
+    o = host_harness.run(exe, tmp, hdr, [per], (B, 43))
     return o[:, 1:7], o[:, 7:].reshape(B, 6, 6), o[:, 0]
 
 
@@ -139,20 +111,22 @@ def make_case(dtype, direct, est_bias, use_pfp, B=300, seed=5):
 @pytest.mark.parametrize("dtype,direct,est_bias,use_pfp", GRID, ids=GRID_IDS)
 def test_host_compiled_arithmetic_matches_oracle_predict_then_restatement(harness, tmp_path, dtype, direct, est_bias, use_pfp, predict):
     po, p, rng, x, P, u, z, pfp = make_case(dtype, direct, est_bias, use_pfp)
-    nu, S, nis = run_harness(harness, tmp_path, po, dtype, predict, x, P, u, z, pfp)
     nur, Sr, nisr, _, _ = predict_then_innovation(po, p, x, P, u, z, pfp, predict=predict)
     tol = TOL[dtype]
-    e_nu, e_S, e_nis = rel(nu, nur), rel(S, Sr), float(np.abs(nis / nisr - 1).max())
-    print(f"{dtype} predict={predict}: worst relative nu {e_nu:.2e} S {e_S:.2e} nis {e_nis:.2e}; NIS range {nisr.min():.3g} .. {nisr.max():.3g}")
-    assert np.isfinite(nis).all() and np.array_equal(S, S.transpose(0, 2, 1))
-    assert e_nu < tol["nu"] and e_S < tol["S"] and e_nis < tol["nis"], (e_nu, e_S, e_nis)
+    for exe in harness:                                        # the plain build, then the same file under ASan + UBSan
+        nu, S, nis = run_harness(exe, tmp_path, po, dtype, predict, x, P, u, z, pfp)
+        e_nu, e_S, e_nis = rel(nu, nur), rel(S, Sr), float(np.abs(nis / nisr - 1).max())
+        print(f"{dtype} predict={predict}: worst relative nu {e_nu:.2e} S {e_S:.2e} nis {e_nis:.2e}; NIS range {nisr.min():.3g} .. {nisr.max():.3g}")
+        assert np.isfinite(nis).all() and np.array_equal(S, S.transpose(0, 2, 1))
+        assert e_nu < tol["nu"] and e_S < tol["S"] and e_nis < tol["nis"], (e_nu, e_S, e_nis)
 
 
 def test_not_positive_definite_S_gives_nan(harness, tmp_path):
     po, p, rng, x, P, u, z, pfp = make_case("f64", 1, 1, False, B=8)
     P[3] = -P[3]
-    _, _, nis = run_harness(harness, tmp_path, po, "f64", False, x, P, u, z, None)
-    assert np.isnan(nis[3]) and np.isfinite(np.delete(nis, 3)).all()
+    for exe in harness:
+        _, _, nis = run_harness(exe, tmp_path, po, "f64", False, x, P, u, z, None)
+        assert np.isnan(nis[3]) and np.isfinite(np.delete(nis, 3)).all()
 
 
 @pytest.mark.parametrize("dtype,direct,est_bias,use_pfp", GRID, ids=GRID_IDS)
@@ -178,28 +152,12 @@ def test_displaced_tag_poses_stay_clear_of_the_threshold(harness, tmp_path, dtyp
     assert (~clear).mean() <= 0.01
     acc_ref = nisr <= CHI2_6_099
     assert acc_ref[~out].mean() > 0.9 and acc_ref[out].mean() < 0.1
-    _, _, nis = run_harness(harness, tmp_path, po, dtype, True, x, P, u, z, None)
-    assert np.array_equal((nis <= CHI2_6_099)[clear], acc_ref[clear])
+    for exe in harness:
+        _, _, nis = run_harness(exe, tmp_path, po, dtype, True, x, P, u, z, None)
+        assert np.array_equal((nis <= CHI2_6_099)[clear], acc_ref[clear])
 
 
 # ---------------------------------------------------------------- refusals, before any GPU call
-def _views(batch=100, dtype=_lib.QLE_F32, tag=True):
-    v = _lib.QleDeviceView()
-    v.struct_size = C.sizeof(v); v.device = 0; v.dtype = dtype; v.num_states = 15; v.batch = batch; v.padded_batch = -(-batch // 64) * 64
-    v.state = 0x7F0000000000; v.state_words = 144; v.record_words = 136
-    iv = _lib.QleInputsView()
-    iv.struct_size = C.sizeof(iv); iv.has_tag = int(tag); iv.u = 0x7F1000000000; iv.z = 0x7F2000000000 if tag else None
-    return v, iv
-
-
-def _params(**kw):
-    p = _lib.QleParams()
-    _lib.check(_lib.lib().qle_params_default(C.byref(p)))
-    for k, val in kw.items():
-        setattr(p, k, val)
-    return p
-
-
 def test_library_refuses_before_any_gpu_call(gate_so):
     """No GPU here: a call that got as far as the HIP runtime would return QLE_ERR_HIP (or crash on the fake pointers), not these."""
     G = gate.gate_lib()
@@ -230,10 +188,7 @@ def test_library_refuses_before_any_gpu_call(gate_so):
     assert G.qgt_launch_count() == 0
 
 
-class FakeEkf:
-    batch, dtype, device, num_states = 100, _lib.QLE_F32, 0, 15
-    _h = None
-
+class FakeEkf(side_lib_util.FakeEkf):
     def __init__(self, **kw):
         self.params = _params(**kw)
 

@@ -1,7 +1,7 @@
 """The chi-square gate in front of the fused tick on the GPU (include/qle_gate.h, libqle_gate.so: k_pregate; DeviceIO.tick(chi2_max=...),
 DeviceIO.innovation).
 
-Reference: the dense oracle's prediction_step followed by innovation_ref (test_innovation_cpu.py), on the values the device holds
+Reference: the dense oracle's prediction_step followed by innovation_ref (innovation_util.py), on the values the device holds
 (gate_util.predict_then_innovation); tolerances gate_util.TOL -- those of test_gpu_innovation.py.  Every case runs in both dtypes, both
 orientation methods, est_bias 1 / 0 (full / compact records), with and without per-filter parameters, and in the three kernel
 families of test_gpu_innovation's kernel_family fixture (the tick BEHIND the gate follows the policy; the gate does not change).
@@ -18,7 +18,7 @@ import test_gpu_parity as tp
 from gate_util import TOL, clear_of_threshold, displaced_tag_poses, predict_then_innovation, rel, rot_z
 from quadrotor_landing_amd import devio, gate
 from test_gpu_innovation import BIG, BW, DIST, HEALTHY, Case, _same, grid, kernel_family  # noqa: F401  (kernel_family: autouse fixture)
-from test_innovation_cpu import CHI2_6_099
+from innovation_util import CHI2_6_099
 from util import assert_state_close, meas_near, rand_imu
 
 pytestmark = pytest.mark.gpu

@@ -164,9 +164,8 @@ def test_mixing_does_not_depend_on_where_the_bank_sits(M, G, dtype, record, monk
 # ------------------------------------------------------------------------------------------------ 5. the recursion
 @pytest.mark.parametrize("M,G", iu.SHAPES, ids=[f"M{M}-G{G}" for M, G in iu.SHAPES])
 def test_update_matches_the_truth(M, G, monkeypatch):
-    from test_imm_cpu import update_case
     c = Case(M, G, "f32", "full15", monkeypatch, seed=4400 + M, specials=False, empty_bank=False)
-    logc, loglik, mask = update_case(c.rng, M, G)
+    logc, loglik, mask = iu.update_case(c.rng, M, G)
     x0, P0 = stored(c)
     for lo in (np.log(1e-12), -np.inf, -3.0):
         ref, scale = iu.update_ref(logc, loglik, mask, lo, M)

@@ -1,6 +1,6 @@
 """Innovation diagnostics (qle_innovation) and the chi-square outlier gate (qle_update_gated, qle_step_gated) on the device.
 
-Reference: innovation_ref (test_innovation_cpu.py), the numpy restatement of the first half of correction_step
+Reference: innovation_ref (innovation_util.py), the numpy restatement of the first half of correction_step
 (relative_pose_EKF.cpp:417-475), evaluated on the values the device holds (the state read back, tag poses and per-filter noise rounded
 to the compute dtype).  Every case runs in both dtypes, both orientation methods, full and compact records (est_bias 1 / 0), with and
 without per-filter parameters and in the three kernel families of test_gpu_isolation.py (QLE_QUAD unset / 0 / 3: the gated tick's
@@ -20,7 +20,7 @@ import quadrotor_landing_amd as qla
 from quadrotor_landing_amd._lib import QLE_ERR_INVALID, QLE_ERR_STATE
 import test_gpu_parity as tp
 from oracle import ekf_np
-from test_innovation_cpu import CHI2_6_099, innovation_ref_batch
+from innovation_util import CHI2_6_099, innovation_ref_batch
 from util import assert_state_close, meas_near, qmul, rand_imu, rand_states
 
 pytestmark = pytest.mark.gpu

@@ -19,7 +19,7 @@ import variant_table as vt
 from oracle import ekf_np
 from test_gpu_innovation import TOL as INNOV_TOL
 from test_gpu_parity import F32, F32U, F64, F64U, HW, HW_TAGS, free_run_close
-from test_innovation_cpu import CHI2_6_099, innovation_ref_batch
+from innovation_util import CHI2_6_099, innovation_ref_batch
 from util import assert_state_close, meas_near, rand_imu, rand_states
 
 pytestmark = pytest.mark.gpu

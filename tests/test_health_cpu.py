@@ -10,41 +10,31 @@ kernel's loads, its masks and its batch summary: tests/test_gpu_lifecycle.py.
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import health_util as hu
-import test_variant_table_cpu as tv
+import host_harness
+from elf_util import _kernels, _needed
 from quadrotor_landing_amd import _lib, consistency, devio, gate, health
-from test_devio_cpu import FakeTensor, _kernels, _needed
+from side_lib_util import (FakeEkf, FakeTensor, _view, assert_audit_counts, assert_exports_and_binds, ensure_built, kernel_descriptors, run_audit,
+                           scratch_free)
 from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "qle_health.h")
 N_KERNELS = 10   # k_health: T x {compact, full n = 9, full n = 15}; k_health_reduce; k_retire: T; k_and_masks
 
 
 @pytest.fixture(scope="module")
 def health_so():
-    if not os.path.exists(health.HEALTH_LIB_PATH):
-        subprocess.run(["make", "-C", CSRC, "../libqle_health.so"], check=True)
-    return health.HEALTH_LIB_PATH
+    return ensure_built("health")
 
 
 def test_library_exports_and_binds_every_declared_function(health_so):
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(qhl_[a-z0-9_]+)\s*\(", txt)))
-    assert names == ["qhl_and_masks", "qhl_health", "qhl_health_host", "qhl_last_error", "qhl_launch_count", "qhl_retire"]
-    L = health.health_lib()
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/qle_health.h but not exported"
-    assert sorted(health.SYMBOLS) == names
-    d = open(health_so, "rb").read()
-    exported = {s for s in tv._symbols(d, 11) if s.startswith("qhl_")}   # SHT_DYNSYM
-    assert exported == set(names), sorted(exported ^ set(names))
+    assert_exports_and_binds(health, HEADER, "qhl", health_so,
+                             ["qhl_and_masks", "qhl_health", "qhl_health_host", "qhl_last_error", "qhl_launch_count", "qhl_retire"])
 
 
 def test_seed_from_a_slot_is_exported_from_the_tick_library():
@@ -91,15 +81,11 @@ def test_library_links_the_hip_runtime_only(health_so):
 
 @pytest.fixture(scope="module")
 def audit(health_so):
-    r = subprocess.run(["make", "-C", CSRC, "audit-health"], capture_output=True, text=True, timeout=900)
-    return r, os.path.join(CSRC, "build", "asm", "health_capi.s")
+    return run_audit("health")
 
 
 def test_generated_device_code_passes_the_stale_exec_audit(audit):
-    r, _ = audit
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    m = re.search(r"audit-health: no register copy under a stale EXEC in (\d+) kernels", r.stdout)
-    assert m and int(m.group(1)) == N_KERNELS, r.stdout[-2000:]
+    assert_audit_counts(audit[0], "health", N_KERNELS)
 
 
 def test_no_kernel_uses_scratch_memory(audit):
@@ -108,31 +94,17 @@ def test_no_kernel_uses_scratch_memory(audit):
     registers that leave room for two waves per SIMD."""
     r, asm = audit
     assert r.returncode == 0
-    txt = open(asm).read()
-    found = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, flags=re.S):
-        name = _lib.demangle(m.group(1))
-        scratch = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", m.group(2)).group(1))
-        lds = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", m.group(2)).group(1))
-        vgpr = int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", m.group(2)).group(1))
-        found[name] = (scratch, lds, vgpr)
+    found, meta = kernel_descriptors(asm)
     assert len([k for k in found if "k_health<" in k]) == 6 and len(found) == N_KERNELS, sorted(found)
     for name, (scratch, lds, vgpr) in found.items():
         print(f"{name.split('(')[0]}: scratch {scratch} B, LDS {lds} B, registers {vgpr}")
         assert scratch == 0, (name, scratch)
         assert lds == (2048 if "k_health_reduce" in name else 0), (name, lds)
         assert vgpr <= (256 if "k_health<float" in name else 512), (name, vgpr)
-    assert all(re.search(r"\.private_segment_fixed_size:\s+0\b", s) for s in re.findall(r"\.private_segment_fixed_size:.*", txt))
+    assert scratch_free(meta), meta
 
 
 # ---------------------------------------------------------------- refusals, before any GPU call
-def _view(batch=100, dtype=_lib.QLE_F32, n=15):
-    v = _lib.QleDeviceView()
-    v.struct_size = C.sizeof(v); v.device = 0; v.dtype = dtype; v.num_states = n; v.batch = batch; v.padded_batch = -(-batch // 64) * 64
-    v.state = 0x7F0000000000; v.state_words = 144; v.record_words = 136
-    return v
-
-
 def test_library_refuses_before_any_gpu_call(health_so):
     """No GPU here: a call that got as far as the HIP runtime would return QLE_ERR_HIP (or crash on the fake pointers), not these."""
     H = health.health_lib()
@@ -175,11 +147,6 @@ def test_library_refuses_before_any_gpu_call(health_so):
     assert H.qhl_health_host(B(v), B(bad), None, p8, None, B(s)) == INV and H.qhl_health_host(B(short), B(lim), None, p8, None, B(s)) == INV
     assert H.qhl_health_host(None, B(lim), None, p8, None, B(s)) == INV
     assert H.qhl_launch_count() == 0
-
-
-class FakeEkf:
-    batch, dtype, device, num_states = 100, _lib.QLE_F32, 0, 15
-    _h = None
 
 
 def test_deviceio_refuses_bad_lifecycle_arguments_before_any_gpu_call(monkeypatch):
@@ -230,35 +197,17 @@ def test_select_names():
 
 
 # ---------------------------------------------------------------- the classification on the host
-SRC = os.path.join(ROOT, "tests", "cpp", "health_harness.cpp")
-GXX = ["g++", "-std=c++17", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-       "-Wno-maybe-uninitialized", "-Wno-unused-but-set-variable"]
-
-
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
     """tests/cpp/health_harness.cpp: ekf_health.hpp's health_classify compiled by g++ (the HIP headers define the device decorators
     away), once as it is and once as a stand-alone program under AddressSanitizer and UBSan."""
-    d = tmp_path_factory.mktemp("hh")
-    plain, san = str(d / "health_harness"), str(d / "health_harness_san")
-    subprocess.run(GXX + ["-O2", "-o", plain, SRC], check=True)
-    subprocess.run(GXX + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", san, SRC], check=True)
-    return plain, san
+    return host_harness.build("health_harness", tmp_path_factory)
 
 
 def run_harness(exe, tmp, dtype, n, compact, x, P, limits, select=63):
     B = x.shape[0]
-    P15 = np.full((B, 15, 15), np.nan if compact else 0.0); P15[:, :n, :n] = P
-    if n == 9 and not compact:
-        P15[:, 9:, :] = 0.0; P15[:, :, 9:] = 0.0   # a full record of a filter without bias states holds zeros there
-    per = np.concatenate([x, P15.reshape(B, 225)], axis=1)
-    fin, fout = str(tmp / "in.bin"), str(tmp / "out.bin")
     hdr = [B, int(dtype == "f64"), int(compact), n, limits["sigma_r_max"], limits["sigma_v_max"], limits["sigma_theta_max"], limits["qnorm_tol"], select]
-    with open(fin, "wb") as fh:
-        np.asarray(hdr, np.float64).tofile(fh); np.ascontiguousarray(per, np.float64).tofile(fh)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0 and int(r.stdout) == B, (r.returncode, r.stdout, r.stderr[-3000:])
-    o = np.fromfile(fout, np.float64).reshape(B, 2)
+    o = host_harness.run(exe, tmp, hdr, [np.concatenate([x, host_harness.full_P(P, compact)], axis=1)], (B, 2))
     return o[:, 0].astype(np.uint8), o[:, 1] != 0
 
 

@@ -17,44 +17,35 @@ Measured deviations of the host-compiled arithmetic from the truth (printed per 
 tests/tolerances_imm.md.
 """
 import ctypes as C
+import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import bank_util as bu
+import host_harness
 import imm_util as iu
-import test_variant_table_cpu as tv
+import side_lib_util
+from elf_util import _kernels, _needed
 from quadrotor_landing_amd import _lib, devio, imm
-from test_devio_cpu import FakeTensor, _kernels, _needed
+from side_lib_util import FakeTensor, assert_audit_counts, assert_exports_and_binds, ensure_built, kernel_descriptors, run_audit, scratch_free
 from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "qle_imm.h")
 N_KERNELS = 5   # k_imm_mix: T x COMPACT, and k_imm_update
 
 
 @pytest.fixture(scope="module")
 def imm_so():
-    if not os.path.exists(imm.IMM_LIB_PATH):
-        subprocess.run(["make", "-C", CSRC, "../libqle_imm.so"], check=True)
-    return imm.IMM_LIB_PATH
+    return ensure_built("imm")
 
 
 # ---------------------------------------------------------------- 1. header, exports, kernels, audit, resources
 def test_library_exports_and_binds_every_declared_function(imm_so):
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(qim_[a-z0-9_]+)\s*\(", txt)))
-    assert names == ["qim_last_error", "qim_launch_count", "qim_mix", "qim_mix_host", "qim_update"]
-    L = imm.imm_lib()
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/qle_imm.h but not exported"
-    assert sorted(imm.SYMBOLS) == names
-    exported = {s for s in tv._symbols(open(imm_so, "rb").read(), 11) if s.startswith("qim_")}   # SHT_DYNSYM
-    assert exported == set(names), sorted(exported ^ set(names))
+    assert_exports_and_binds(imm, HEADER, "qim", imm_so, ["qim_last_error", "qim_launch_count", "qim_mix", "qim_mix_host", "qim_update"])
 
 
 def test_kernels_are_its_own_and_exactly_five(imm_so):
@@ -77,15 +68,11 @@ def test_library_links_the_hip_runtime_only(imm_so):
 
 @pytest.fixture(scope="module")
 def audit(imm_so):
-    r = subprocess.run(["make", "-C", CSRC, "audit-imm"], capture_output=True, text=True, timeout=900)
-    return r, os.path.join(CSRC, "build", "asm", "imm_capi.s")
+    return run_audit("imm")
 
 
 def test_generated_device_code_passes_the_stale_exec_audit(audit):
-    r, _ = audit
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    m = re.search(r"audit-imm: no register copy under a stale EXEC in (\d+) kernels", r.stdout)
-    assert m and int(m.group(1)) == N_KERNELS, r.stdout[-2000:]
+    assert_audit_counts(audit[0], "imm", N_KERNELS)
 
 
 def test_no_kernel_uses_scratch_memory_or_lds(audit):
@@ -93,29 +80,18 @@ def test_no_kernel_uses_scratch_memory_or_lds(audit):
     LDS for all five.  One wave per workgroup: the register file of a SIMD (512 per lane) is the limit, not 256."""
     r, asm = audit
     assert r.returncode == 0
-    txt = open(asm).read()
-    found = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, flags=re.S):
-        name = _lib.demangle(m.group(1))
-        scratch = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", m.group(2)).group(1))
-        lds = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", m.group(2)).group(1))
-        vgpr = int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", m.group(2)).group(1))
-        found[name] = (scratch, lds, vgpr)
+    found, meta = kernel_descriptors(asm)
     assert len(found) == N_KERNELS and all("k_imm_" in k for k in found), sorted(found)
     for name, (scratch, lds, vgpr) in found.items():
         print(f"{name.split('(')[0]}: scratch {scratch} B, LDS {lds} B, registers {vgpr}")
         assert scratch == 0, (name, scratch)
         assert lds == 0, (name, lds)
         assert vgpr <= 512, (name, vgpr)
-    assert all(re.search(r"\.private_segment_fixed_size:\s+0\b", s) for s in re.findall(r"\.private_segment_fixed_size:.*", txt))
+    assert scratch_free(meta), meta
 
 
 # ---------------------------------------------------------------- 2. refusals, before any GPU call
-def _view(batch=128, dtype=_lib.QLE_F32, n=15, compact=0):
-    v = _lib.QleDeviceView()
-    v.struct_size = C.sizeof(v); v.device = 0; v.dtype = dtype; v.num_states = n; v.batch = batch; v.padded_batch = -(-batch // 64) * 64
-    v.state = 0x7F0000000000; v.state_words = 144; v.record_words = 64 if compact else 136; v.compact = compact
-    return v
+_view = functools.partial(side_lib_util._view, batch=128)
 
 
 def test_library_refuses_before_any_gpu_call(imm_so):
@@ -334,35 +310,17 @@ def test_truth_with_an_identity_Pi_mixes_nothing(M, n):
 
 
 # ---------------------------------------------------------------- 5. the arithmetic on the host, once more under the sanitizers
-SRC = os.path.join(ROOT, "tests", "cpp", "imm_harness.cpp")
-GXX = ["g++", "-std=c++17", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-       "-Wno-maybe-uninitialized", "-Wno-unused-but-set-variable"]
-
-
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
     """tests/cpp/imm_harness.cpp: the arithmetic of ekf_imm.hpp compiled by g++ (the HIP headers define the device decorators away),
     once as it is and once as a stand-alone program under AddressSanitizer and UBSan."""
-    d = tmp_path_factory.mktemp("imm")
-    plain, san = str(d / "imm_harness"), str(d / "imm_harness_san")
-    subprocess.run(GXX + ["-O2", "-o", plain, SRC], check=True)
-    subprocess.run(GXX + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", san, SRC], check=True)
-    return plain, san
+    return host_harness.build("imm_harness", tmp_path_factory)
 
 
 def run_mix(exe, tmp, dtype, compact, M, x, P, logmu, mask, Pi):
     B, n = x.shape[0], P.shape[1]
-    P15 = np.full((B, 15, 15), np.nan if compact else 0.0); P15[:, :n, :n] = P   # compact: the words outside the pose block do not exist
-    if n == 9 and not compact:
-        P15[:, 9:, :] = 0.0; P15[:, :, 9:] = 0.0
-    per = np.concatenate([x, P15.reshape(B, 225), logmu[:, None], mask[:, None].astype(np.float64)], axis=1)
-    fin, fout = str(tmp / "in.bin"), str(tmp / "out.bin")
-    with open(fin, "wb") as fh:
-        np.asarray([B, int(dtype == "f64"), int(compact), M], np.float64).tofile(fh); np.ascontiguousarray(Pi, np.float64).tofile(fh)
-        np.ascontiguousarray(per, np.float64).tofile(fh)
-    r = subprocess.run([exe, "mix", fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "" and int(r.stdout) == B, (r.returncode, r.stdout, r.stderr[-3000:])
-    o = np.fromfile(fout, np.float64).reshape(B, 243)
+    per = np.concatenate([x, host_harness.full_P(P, compact), logmu[:, None], mask[:, None].astype(np.float64)], axis=1)
+    o = host_harness.run(exe, tmp, [B, int(dtype == "f64"), int(compact), M], [Pi, per], (B, 243), argv=("mix",))
     Pm = o[:, 18:].reshape(B, 15, 15)
     assert not Pm[:, n:, :].any() and not Pm[:, :, n:].any()
     return o[:, 0], o[:, 1] != 0, o[:, 2:18], Pm[:, :n, :n].copy()
@@ -392,36 +350,10 @@ def test_host_compiled_mixing_matches_the_truth(harness, tmp_path, M, G, dtype, 
         assert all(dev[k] <= tol[k] for k in dev), (dev, tol)
 
 
-def update_case(rng, M, G):
-    """(logc, loglik, mask) with the members the recursion treats specially: per bank a loglik of -inf, a NaN one, a masked member and
-    a logc of -inf (M >= 8: all four; M = 2: one in turn), loglik otherwise spread over tens of nats; the last bank has no member left."""
-    B = M * G
-    logc = np.log(rng.dirichlet(np.ones(M), size=G)).reshape(B)
-    loglik = rng.uniform(-40.0, 5.0, size=B)
-    mask = np.ones(B, np.uint8)
-    for g in range(G - 1):
-        lanes = rng.permutation(M)[:4] if M >= 8 else [int(rng.integers(M))] * 4
-        for kind, l in enumerate(lanes):
-            if M < 8 and kind != g % 5:
-                continue
-            i = g * M + int(l)
-            if kind == 0:
-                loglik[i] = -np.inf
-            elif kind == 1:
-                loglik[i] = np.nan
-            elif kind == 2:
-                mask[i] = 0
-            else:
-                logc[i] = -np.inf
-    mask[-M::2] = 0
-    logc[-M + 1::2] = -np.inf
-    return logc, loglik, mask
-
-
 @pytest.mark.parametrize("M,G", iu.SHAPES, ids=[f"M{M}" for M, _ in iu.SHAPES])
 def test_host_compiled_recursion_matches_the_truth(harness, tmp_path, M, G):
     rng = np.random.default_rng(3500 + M)
-    logc, loglik, mask = update_case(rng, M, G)
+    logc, loglik, mask = iu.update_case(rng, M, G)
     for lo in (np.log(1e-12), -np.inf, -3.0):
         ref, scale = iu.update_ref(logc, loglik, mask, lo, M)
         if lo > -np.inf:
@@ -430,13 +362,7 @@ def test_host_compiled_recursion_matches_the_truth(harness, tmp_path, M, G):
             assert np.isneginf(ref[np.isneginf(loglik) & (mask != 0) & np.isfinite(logc)]).all()       # -inf leaves -inf
         assert np.isneginf(ref[(mask == 0) | ~np.isfinite(logc)]).all()
         for exe in harness:
-            fin, fout = str(tmp_path / "uin.bin"), str(tmp_path / "uout.bin")
-            with open(fin, "wb") as fh:
-                np.asarray([M * G, M, lo], np.float64).tofile(fh)
-                np.ascontiguousarray(np.stack([logc, loglik, mask.astype(np.float64)], axis=1)).tofile(fh)
-            r = subprocess.run([exe, "update", fin, fout], capture_output=True, text=True)
-            assert r.returncode == 0 and r.stderr == "" and int(r.stdout) == M * G, (r.returncode, r.stdout, r.stderr[-3000:])
-            got = np.fromfile(fout, np.float64)
+            got = host_harness.run(exe, tmp_path, [M * G, M, lo], [np.stack([logc, loglik, mask.astype(np.float64)], axis=1)], -1, argv=("update",))
             np.testing.assert_array_equal(np.isneginf(got), np.isneginf(ref))
             np.testing.assert_array_equal(got == lo, ref == lo)
             fin_ = np.isfinite(ref)

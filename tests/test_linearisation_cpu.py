@@ -17,7 +17,7 @@ import oracle
 import truth_mp as tm
 from linearisation_util import BRANCHES, GOLDEN, HW, THETA_STAR, fixture, params_kw, probe_covs, probes, rel, table
 from oracle import ekf_np
-from test_innovation_cpu import innovation_ref
+from innovation_util import innovation_ref
 from util import cov_dev, quat_err, state_dev
 
 branches = pytest.mark.parametrize("direct,est_bias", BRANCHES, ids=[f"direct{d}-bias{e}" for d, e in BRANCHES])

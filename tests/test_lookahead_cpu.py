@@ -14,42 +14,33 @@ printed per case by test_host_compiled_forecast_matches_h_oracle_predicts (`pyte
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_harness
 import lookahead_util as lu
-import test_variant_table_cpu as tv
+import side_lib_util
+from elf_util import _kernels, _needed
 from quadrotor_landing_amd import _lib, consistency, devio, gate, health, lookahead
-from test_devio_cpu import FakeTensor, _kernels, _needed
+from side_lib_util import (FakeTensor, _params, _view, assert_audit_counts, assert_exports_and_binds, ensure_built, kernel_descriptors,
+                           run_audit, scratch_free)
 from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "qle_lookahead.h")
 N_KERNELS = 8   # k_lookahead: T x PFP x COMPACT
 
 
 @pytest.fixture(scope="module")
 def look_so():
-    if not os.path.exists(lookahead.LOOKAHEAD_LIB_PATH):
-        subprocess.run(["make", "-C", CSRC, "../libqle_lookahead.so"], check=True)
-    return lookahead.LOOKAHEAD_LIB_PATH
+    return ensure_built("lookahead")
 
 
 # ---------------------------------------------------------------- 1. header, exports, kernels
 def test_library_exports_and_binds_every_declared_function(look_so):
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(qlk_[a-z0-9_]+)\s*\(", txt)))
-    assert names == ["qlk_last_error", "qlk_launch_count", "qlk_lookahead", "qlk_lookahead_host", "qlk_workspace_bytes"]
-    L = lookahead.lookahead_lib()
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/qle_lookahead.h but not exported"
-    assert sorted(lookahead.SYMBOLS) == names
-    d = open(look_so, "rb").read()
-    exported = {s for s in tv._symbols(d, 11) if s.startswith("qlk_")}   # SHT_DYNSYM
-    assert exported == set(names), sorted(exported ^ set(names))
+    _, txt = assert_exports_and_binds(lookahead, HEADER, "qlk", look_so,
+                                      ["qlk_last_error", "qlk_launch_count", "qlk_lookahead", "qlk_lookahead_host", "qlk_workspace_bytes"])
     body = re.search(r"typedef struct qlk_coast \{(.*?)\} qlk_coast;", txt, flags=re.S).group(1)
     assert re.findall(r"(?:uint32_t|double)\s+([a-z_]+);", body) == [n for n, _ in lookahead.QlkCoast._fields_]
     assert int(re.search(r"#define QLK_MAX_HORIZON (\d+)", txt).group(1)) == lookahead.MAX_HORIZON == 4096
@@ -81,15 +72,11 @@ def test_library_links_the_hip_runtime_and_the_tick_library_only(look_so):
 # ---------------------------------------------------------------- 2. audit and resources
 @pytest.fixture(scope="module")
 def audit(look_so):
-    r = subprocess.run(["make", "-C", CSRC, "audit-lookahead"], capture_output=True, text=True, timeout=900)
-    return r, os.path.join(CSRC, "build", "asm", "lookahead_capi.s")
+    return run_audit("lookahead")
 
 
 def test_generated_device_code_passes_the_stale_exec_audit(audit):
-    r, _ = audit
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    m = re.search(r"audit-lookahead: no register copy under a stale EXEC in (\d+) kernels", r.stdout)
-    assert m and int(m.group(1)) == N_KERNELS, r.stdout[-2000:]
+    assert_audit_counts(audit[0], "lookahead", N_KERNELS)
 
 
 def test_no_kernel_uses_scratch_memory_or_lds_and_the_registers_fit(audit):
@@ -97,39 +84,17 @@ def test_no_kernel_uses_scratch_memory_or_lds_and_the_registers_fit(audit):
     counts the launch bounds promise -- fp32 within the 256 registers that leave room for two waves per SIMD, fp64 within 512."""
     r, asm = audit
     assert r.returncode == 0
-    txt = open(asm).read()
-    found = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, flags=re.S):
-        name = _lib.demangle(m.group(1))
-        scratch = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", m.group(2)).group(1))
-        lds = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", m.group(2)).group(1))
-        vgpr = int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", m.group(2)).group(1))
-        found[name] = (scratch, lds, vgpr)
+    found, meta = kernel_descriptors(asm)
     assert len(found) == N_KERNELS and all("k_lookahead<" in k for k in found), sorted(found)
     for name, (scratch, lds, vgpr) in found.items():
         print(f"{name.split('(')[0]}: scratch {scratch} B, LDS {lds} B, registers {vgpr}")
         assert scratch == 0, (name, scratch)
         assert lds == 0, (name, lds)
         assert vgpr <= (256 if "k_lookahead<float" in name else 512), (name, vgpr)
-    assert all(re.search(r"\.private_segment_fixed_size:\s+0\b", s) for s in re.findall(r"\.private_segment_fixed_size:.*", txt))
+    assert scratch_free(meta), meta
 
 
 # ---------------------------------------------------------------- 3. refusals, before any GPU call
-def _view(batch=100, dtype=_lib.QLE_F32, n=15, compact=0):
-    v = _lib.QleDeviceView()
-    v.struct_size = C.sizeof(v); v.device = 0; v.dtype = dtype; v.num_states = n; v.batch = batch; v.padded_batch = -(-batch // 64) * 64
-    v.state = 0x7F0000000000; v.state_words = 144; v.record_words = 64 if compact else 136; v.compact = compact
-    return v
-
-
-def _params(**kw):
-    p = _lib.QleParams()
-    _lib.check(_lib.lib().qle_params_default(C.byref(p)))
-    for k, val in kw.items():
-        setattr(p, k, val)
-    return p
-
-
 def _coast(r=1.0, th=0.5):
     c = lookahead.QlkCoast()
     c.struct_size = C.sizeof(c); c.sigma_r_max = r; c.sigma_theta_max = th
@@ -192,10 +157,7 @@ def test_library_refuses_before_any_gpu_call(look_so):
     assert K.qlk_launch_count() == 0
 
 
-class FakeEkf:
-    batch, dtype, device, num_states = 100, _lib.QLE_F32, 0, 15
-    _h = None
-
+class FakeEkf(side_lib_util.FakeEkf):
     def __init__(self, **kw):
         self.params = _params(**kw)
 
@@ -226,38 +188,19 @@ def test_deviceio_refuses_bad_lookahead_arguments_before_any_gpu_call(monkeypatc
 
 
 # ---------------------------------------------------------------- 4. the arithmetic on the host, 5. once more under the sanitizers
-SRC = os.path.join(ROOT, "tests", "cpp", "lookahead_harness.cpp")
-GXX = ["g++", "-std=c++17", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-       "-Wno-maybe-uninitialized", "-Wno-unused-but-set-variable"]
-
-
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
     """tests/cpp/lookahead_harness.cpp: ekf_lookahead.hpp's lookahead_filter compiled by g++ (the HIP headers define the device
     decorators away), once as it is and once as a stand-alone program under AddressSanitizer and UBSan."""
-    d = tmp_path_factory.mktemp("lh")
-    plain, san = str(d / "lookahead_harness"), str(d / "lookahead_harness_san")
-    subprocess.run(GXX + ["-O2", "-o", plain, SRC], check=True)
-    subprocess.run(GXX + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", san, SRC], check=True)
-    return plain, san
+    return host_harness.build("lookahead_harness", tmp_path_factory)
 
 
 def run_harness(exe, tmp, po, dtype, compact, h, x, P, u, pfp, asked=None, sigma_r_max=np.inf, sigma_theta_max=np.inf):
     B, n = x.shape[0], po.num_states
-    hdr = [B, int(dtype == "f64"), int(compact), int(pfp is not None), h, sigma_r_max, sigma_theta_max,
-           po.dT_nom, po.dT_nom if po.est_bias else 0.0, float(po.est_bias), po.small_ang_tol,
-           *po.g, *po.q_vc, *po.C_vc, *po.r_v_cv, *po.Q, *po.R, *po.ab_static, *po.wb_static]
-    P15 = np.full((B, 15, 15), np.nan if compact else 0.0); P15[:, :n, :n] = P   # compact: the words outside the pose block do not exist
-    if n == 9 and not compact:
-        P15[:, 9:, :] = 0.0; P15[:, :, 9:] = 0.0
+    hdr = [B, int(dtype == "f64"), int(compact), int(pfp is not None), h, sigma_r_max, sigma_theta_max, *host_harness.params_header(po)]
     on = np.ones((B, 1)) if asked is None else np.asarray(asked, np.float64).reshape(B, 1)
-    per = np.concatenate([x, P15.reshape(B, 225), u, np.zeros((B, 24)) if pfp is None else pfp, on], axis=1)
-    fin, fout = str(tmp / "in.bin"), str(tmp / "out.bin")
-    with open(fin, "wb") as fh:
-        np.asarray(hdr, np.float64).tofile(fh); np.ascontiguousarray(per, np.float64).tofile(fh)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "" and int(r.stdout) == B, (r.returncode, r.stdout, r.stderr[-3000:])
-    o = np.fromfile(fout, np.float64).reshape(B, 242)
+    per = np.concatenate([x, host_harness.full_P(P, compact), u, np.zeros((B, 24)) if pfp is None else pfp, on], axis=1)
+    o = host_harness.run(exe, tmp, hdr, [per], (B, 242))
     P = o[:, 16:241].reshape(B, 15, 15)
     if compact:
         assert np.isnan(P[:, 9:, :]).all() and np.isnan(P[:, :, 9:]).all()

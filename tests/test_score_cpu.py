@@ -14,47 +14,32 @@ parameters, 64 filters, 5 ticks; each word relative to its sum of absolute terms
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_harness
 import oracle
-import test_variant_table_cpu as tv
+from elf_util import _kernels
+from gate_util import HW, predict_then_innovation
 from oracle import ekf_np
 from quadrotor_landing_amd import _lib, score
 from score_util import COUNTS, PREV, TOL, ScoreRef, deviations, make_sequence
-from gate_util import predict_then_innovation
-from test_devio_cpu import _kernels
-from test_gate_cpu import HW, _params, _views
+from side_lib_util import _params, _views, assert_audit_counts, assert_exports_and_binds, ensure_built, run_audit
 from util import forbid_native, rand_states
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "qle_score.h")
-SRC = os.path.join(ROOT, "tests", "cpp", "score_harness.cpp")
-GXX = ["g++", "-std=c++17", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-       "-Wno-maybe-uninitialized"]
 
 
 @pytest.fixture(scope="module")
 def score_so():
-    if not os.path.exists(score.SCORE_LIB_PATH):
-        subprocess.run(["make", "-C", CSRC, "../libqle_score.so"], check=True)
-    return score.SCORE_LIB_PATH
+    return ensure_built("score")
 
 
 def test_library_exports_and_binds_every_declared_function(score_so):
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(qsc_[a-z0-9_]+)\s*\(", txt)))
-    assert names == ["qsc_last_error", "qsc_launch_count", "qsc_run", "qsc_run_host", "qsc_score_tick", "qsc_summary"]
-    L = score.score_lib()
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/qle_score.h but not exported"
-    assert sorted(score.SYMBOLS) == names
-    d = open(score_so, "rb").read()
-    exported = {s for s in tv._symbols(d, 11) if s.startswith("qsc_")}   # SHT_DYNSYM
-    assert exported == set(names), sorted(exported ^ set(names))
+    _, txt = assert_exports_and_binds(score, HEADER, "qsc", score_so,
+                                      ["qsc_last_error", "qsc_launch_count", "qsc_run", "qsc_run_host", "qsc_score_tick", "qsc_summary"])
     assert score.WORDS == int(re.search(r"#define QSC_WORDS (\d+)", txt).group(1)) == 40
     assert score.SUMS == int(re.search(r"#define QSC_SUMS (\d+)", txt).group(1)) == 30
 
@@ -76,10 +61,7 @@ def test_library_needs_the_tick_library_and_no_other(score_so):
 
 
 def test_generated_device_code_passes_the_stale_exec_audit(score_so):
-    r = subprocess.run(["make", "-C", CSRC, "audit-score"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    m = re.search(r"audit-score: no register copy under a stale EXEC in (\d+) kernels", r.stdout)
-    assert m and int(m.group(1)) == 18, r.stdout[-2000:]
+    assert_audit_counts(run_audit("score")[0], "score", 18)
 
 
 # ---------------------------------------------------------------- refusals, before any GPU call
@@ -159,11 +141,7 @@ def test_score_reads_the_accumulator_words():
 def harness(tmp_path_factory):
     """tests/cpp/score_harness.cpp: score_accumulate and pregate_eval_pivots compiled by g++ (the HIP headers define the device decorators
     away), once as it is and once as a stand-alone program under AddressSanitizer and UBSan."""
-    d = tmp_path_factory.mktemp("sch")
-    plain, san = str(d / "score_harness"), str(d / "score_harness_san")
-    subprocess.run(GXX + ["-O2", "-o", plain, SRC], check=True)
-    subprocess.run(GXX + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", san, SRC], check=True)
-    return plain, san
+    return host_harness.build("score_harness", tmp_path_factory)
 
 
 TICKS, NF = 5, 64
@@ -171,21 +149,11 @@ TICKS, NF = 5, 64
 
 def run_harness(exe, tmp, po, dtype, states, U, Z, ON, pfp):
     """states: [(x, P)] in front of every tick; -> acc [B, 40]"""
-    B, n = NF, po.num_states
-    hdr = [B, po.direct_orien_method, TICKS, int(pfp is not None), int(dtype == "f64"),
-           po.dT_nom, po.dT_nom if po.est_bias else 0.0, float(po.est_bias), po.small_ang_tol,
-           *po.g, *po.q_vc, *po.C_vc, *po.r_v_cv, *po.Q, *po.R, *po.ab_static, *po.wb_static]
-    fin, fout = str(tmp / "in.bin"), str(tmp / "out.bin")
-    with open(fin, "wb") as fh:
-        np.asarray(hdr, np.float64).tofile(fh)
-        for t in range(TICKS):
-            x, P = states[t]
-            P15 = np.zeros((B, 15, 15)); P15[:, :n, :n] = P
-            per = np.concatenate([x, P15.reshape(B, 225), U[t], Z[t], np.zeros((B, 24)) if pfp is None else pfp, ON[t][:, None].astype(np.float64)], axis=1)
-            np.ascontiguousarray(per, np.float64).tofile(fh)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0 and int(r.stdout) == B, (r.returncode, r.stdout, r.stderr[-3000:])   # a sanitizer report ends it with a non-zero status
-    return np.fromfile(fout, np.float64).reshape(B, 40)
+    B = NF
+    hdr = [B, po.direct_orien_method, TICKS, int(pfp is not None), int(dtype == "f64"), *host_harness.params_header(po)]
+    per = [np.concatenate([x, host_harness.full_P(P), U[t], Z[t], np.zeros((B, 24)) if pfp is None else pfp, ON[t][:, None].astype(np.float64)], axis=1)
+           for t, (x, P) in enumerate(states)]
+    return host_harness.run(exe, tmp, hdr, per, (B, 40))
 
 
 GRID = [(d, o, f) for d in ("f64", "f32") for o in (1, 0) for f in (False, True)]

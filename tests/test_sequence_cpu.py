@@ -12,31 +12,25 @@ import subprocess
 import numpy as np
 import pytest
 
-import test_devio_cpu as td
+import host_harness
+import side_lib_util
+from elf_util import _kernels, _needed
 from quadrotor_landing_amd import _lib, devio, sequence
+from side_lib_util import (FakeTensor, _Reader, _view, assert_audit_counts, assert_exports_and_binds, ensure_built, kernel_descriptors,
+                           run_audit, scratch_free)
 from util import forbid_native
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "quadrotor_landing_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "qle_sequence.h")
 
 
 @pytest.fixture(scope="module")
 def sequence_so():
-    if not os.path.exists(sequence.SEQUENCE_LIB_PATH):
-        subprocess.run(["make", "-C", CSRC, "../libqle_sequence.so"], check=True)
-    return sequence.SEQUENCE_LIB_PATH
+    return ensure_built("sequence")
 
 
 def test_library_exports_and_binds_every_declared_function(sequence_so):
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(qsq_[a-z0-9_]+)\s*\(", txt)))
-    assert names == ["qsq_last_error", "qsq_launch_count", "qsq_pack", "qsq_run"]
-    L = C.CDLL(sequence_so)
-    for n in names:
-        assert hasattr(L, n), f"{n} declared in include/qle_sequence.h but not exported"
-    assert sorted(sequence.SYMBOLS) == names
-    assert sequence.sequence_lib() is not None
+    _, txt = assert_exports_and_binds(sequence, HEADER, "qsq", sequence_so, ["qsq_last_error", "qsq_launch_count", "qsq_pack", "qsq_run"])
     assert sequence.CHUNK == int(re.search(r"#define QSQ_CHUNK (\d+)", txt).group(1)) == 32
 
 
@@ -59,15 +53,11 @@ def test_run_opts_layout_matches_the_header(tmp_path):
 
 @pytest.fixture(scope="module")
 def audit(sequence_so):
-    r = subprocess.run(["make", "-C", CSRC, "audit-sequence"], capture_output=True, text=True, timeout=600)
-    return r, os.path.join(CSRC, "build", "asm", "sequence_capi.s")
+    return run_audit("sequence")
 
 
 def test_generated_device_code_passes_the_stale_exec_audit(audit):
-    r, _ = audit
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    m = re.search(r"audit-sequence: no register copy under a stale EXEC in (\d+) kernels", r.stdout)
-    assert m and int(m.group(1)) >= 1, r.stdout[-2000:]
+    assert_audit_counts(audit[0], "sequence")
 
 
 def test_no_kernel_uses_scratch_memory(audit):
@@ -75,36 +65,32 @@ def test_no_kernel_uses_scratch_memory(audit):
     (compute dtype, source dtype) instantiations of k_sq_pack, and the two LDS images of 64 x 7 words."""
     r, asm = audit
     assert r.returncode == 0
-    txt = open(asm).read()
-    found = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, flags=re.S):
-        get = lambda key: int(re.search(rf"\.amdhsa_{key} (\d+)", m.group(2)).group(1))   # noqa: E731
-        found[_lib.demangle(m.group(1)).split("(")[0]] = (get("private_segment_fixed_size"), get("next_free_vgpr"), get("group_segment_fixed_size"))
+    found, meta = kernel_descriptors(asm)
+    found = {name.split("(")[0]: d for name, d in found.items()}
     assert sorted(found) == [f"void qsq::k_sq_pack<{t}, {s}>" for t in ("double", "float") for s in ("double", "float")], sorted(found)
-    for name, (scratch, vgpr, lds) in found.items():
+    for name, (scratch, lds, vgpr) in found.items():
         print(f"{name}: scratch {scratch} B, registers {vgpr}, LDS {lds} B")
         assert scratch == 0, (name, scratch)
         assert lds == 2 * 64 * 7 * (8 if "<double" in name else 4), (name, lds)
-    meta = re.findall(r"\.private_segment_fixed_size:.*", txt)
-    assert len(meta) == 4 and all(re.search(r":\s+0\b", s) for s in meta), meta
+    assert len(meta) == 4 and scratch_free(meta), meta
 
 
 def test_kernels_are_its_own_and_all_k_sq_pack(sequence_so):
-    mine = td._kernels(sequence_so)
+    mine = _kernels(sequence_so)
     assert mine
     for other in (_lib.LIB_PATH, devio.DEVIO_LIB_PATH):
-        theirs = td._kernels(other)
+        theirs = _kernels(other)
         assert theirs and not mine & theirs, sorted(mine & theirs)
         assert not any("qsq::" in _lib.demangle(m) for m in theirs)
     ids = {_lib.demangle(m) for m in mine}
     assert all(i.startswith("void qsq::k_sq_pack<") for i in ids) and len(ids) == 4, sorted(ids)
     # the boundary library keeps exactly its three families: the record stores the two packs share are inlined helpers, not kernels
-    fam = {_lib.demangle(m).split("<")[0].split("::")[1] for m in td._kernels(devio.DEVIO_LIB_PATH)}
+    fam = {_lib.demangle(m).split("<")[0].split("::")[1] for m in _kernels(devio.DEVIO_LIB_PATH)}
     assert fam == {"k_dv_pack", "k_dv_state", "k_dv_report"}, fam
 
 
 def test_library_links_the_four_it_drives(sequence_so):
-    needed = td._needed(sequence_so)
+    needed = _needed(sequence_so)
     for lib in ("libqle_ekf.so", "libqle_devio.so", "libqle_gate.so", "libqle_consistency.so"):
         assert lib in needed, needed
     d = open(sequence_so, "rb").read()
@@ -115,10 +101,8 @@ def test_library_links_the_four_it_drives(sequence_so):
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
     """tests/cpp/sequence_harness.cpp built with g++ under ASan + UBSan and run directly, nothing preloaded."""
-    d = tmp_path_factory.mktemp("sqh")
-    exe, out = str(d / "sqh"), str(d / "sqh.bin")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                    os.path.join(ROOT, "tests", "cpp", "sequence_harness.cpp")], check=True)
+    exe, = host_harness.build("sequence_harness", tmp_path_factory, plain=False, flags=("-Wall", "-Werror"))
+    out = exe + ".bin"
     r = subprocess.run([exe, out], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]   # a sanitizer report ends the program with a non-zero status
     data = np.fromfile(out, dtype=np.int64)
@@ -127,7 +111,7 @@ def harness(tmp_path_factory):
 
 
 def test_staging_walk_moves_every_valid_word_once_and_nothing_else(harness):
-    rd = td._Reader(harness)
+    rd = _Reader(harness)
     # head words in front of the next 16-byte boundary
     np.testing.assert_array_equal(rd.take(8), [0, 3, 2, 1, 0, 3, 2, 1])
     np.testing.assert_array_equal(rd.take(4), [0, 1, 0, 1])
@@ -154,7 +138,7 @@ def test_staging_walk_moves_every_valid_word_once_and_nothing_else(harness):
 
 
 def test_plan_puts_every_tick_in_one_chunk_entry(harness):
-    rd = td._Reader(harness)
+    rd = _Reader(harness)
     rd.take(12 + sum(2 * nv * W + 6 for V in (4, 2) for _ in range(V) for W in (6, 7) for nv in (0, 1, 23, 63, 64)))
     tagged = {0, 3, 31, 32, 33, 64, 69}
     for n in (1, 31, 32, 33, 70):
@@ -184,7 +168,7 @@ class FakeParams:
     multirate_ekf = 0
 
 
-class FakeEkf(td.FakeEkf):
+class FakeEkf(side_lib_util.FakeEkf):
     params = FakeParams()
 
 
@@ -199,7 +183,7 @@ def test_sequence_and_run_refuse_before_any_gpu_call(monkeypatch):
     monkeypatch.setattr(FakeEkf, "make_inputs", boom, raising=False)
     io = devio.DeviceIO(FakeEkf())
     B, K = 100, 40
-    T = td.FakeTensor
+    T = FakeTensor
     u = T((K, B, 6))
     z3, m3 = T((3, B, 7)), T((3, B), dtype="uint8")
     bad = [
@@ -290,9 +274,7 @@ def _opts(**kw):
 def test_native_entries_refuse_before_any_gpu_call(sequence_so):
     """Without a GPU a HIP call fails as QLE_ERR_HIP / QLE_ERR_NO_DEVICE: every refusal here is QLE_ERR_INVALID with its own message."""
     S = sequence.sequence_lib()
-    v = _lib.QleDeviceView()
-    v.struct_size = C.sizeof(v); v.device = 0; v.dtype = _lib.QLE_F32; v.num_states = 15; v.batch = 100; v.padded_batch = 128
-    v.state = 0x7F0000000000; v.state_words = 144; v.record_words = 136
+    v = _view()
     u = C.c_void_p(0x7F0000100000)
     assert S.qsq_pack(None, None, 0, 1, u, None, None, 0) == _lib.QLE_ERR_INVALID
     assert S.qsq_pack(C.byref(v), None, 0, 1, u, None, None, 0) == _lib.QLE_ERR_INVALID and b"inputs is null" in S.qsq_last_error()
