@@ -367,7 +367,8 @@ typedef struct qle_device_view {
     int32_t record_words;    /* words of it a tick reads and writes: 136, or 64 compact  */
     int32_t compact;         /* != 0: words 16..60 are the row-major triangle of the 9 x 9 pose block (ekf_layout.hpp) */
     int32_t reserved;
-    const void *filter_params; /* 24-word per-filter parameter records while qle_set_filter_params is in force, else NULL */
+    void *filter_params;     /* 24-word per-filter parameter records while qle_set_filter_params is in force, else NULL; read by
+                              * every consumer but qle_adapt.h, which writes words 18..23 (R) through it on `stream` */
     double ab_static[3];     /* the static biases qle_get_report adds (NODE.cpp:215-220), as the compute dtype holds them */
     double wb_static[3];
 } qle_device_view;

@@ -6,6 +6,7 @@ from .twin import RelativePoseEKF  # noqa: F401
 from .devio import DeviceIO  # noqa: F401
 from .params import default_params, derive, load_yaml, make_params, set_fields  # noqa: F401
 from . import replay  # noqa: F401
+from . import adapt  # noqa: F401
 from . import bank  # noqa: F401
 from . import consistency  # noqa: F401
 from . import health  # noqa: F401

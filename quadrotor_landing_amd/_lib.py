@@ -180,7 +180,7 @@ def check(rc):
 
 
 class SideLibrary:
-    """One of the libraries beside libqle_ekf.so (devio, gate, consistency, health, lookahead, sequence, score, bank, imm): where it is
+    """One of the libraries beside libqle_ekf.so (devio, gate, consistency, health, lookahead, sequence, score, bank, imm, adapt): where it is
     (`env` names the environment variable that overrides the in-tree path), what it exports (`symbols`, name -> (restype, argtypes)),
     `what` it is for (the error text when it is missing), the name of its `*_last_error`, and what has to be loaded in front of it.
     needs_tick_library: the library takes qle_params_derive from the tick library, which is loaded first so that it is the same copy

@@ -488,7 +488,9 @@ static int stage_P(qle_batch* h, H* P, void* rec)
 // history starts at tick - 1"
 template <typename I>
 static int seed_prev_tick(qle_batch* h, I* ticks) { return launch(h, k_fill_i32<I>, grid_for(h, 256), dim3(256), 0, ticks, (I)(h->tick - 1), h->B); }
-// per-filter parameters are allocated by whichever call first provides them (qle_set_filter_params, the generator)
+// per-filter parameters are allocated by whichever call first provides them (qle_set_filter_params, the generator).  The device records
+// are the only copy: libqle_adapt.so writes words 18..23 (R) through the view's filter_params on the handle's stream, and
+// qle_get_filter_params reads the adapted values back -- no host copy of them exists that could go stale.
 static int need_pfp(qle_batch* h)
 {
     if (h->pfp) return QLE_OK;

@@ -1,12 +1,12 @@
 // score_capi.hip -- C ABI of include/qle_score.h over ekf_score.hpp.  Host side: argument checks (every refusal before any GPU call),
 // ONE launch per scored tick on the view's stream, the C loop of qsc_run over qsc's own launch and qle_run of the tick library, and the
 // two launches of the batch summary.  Links libqle_ekf.so for qle_params_derive, the two view calls and qle_run, and derives the
-// launch's parameter block as the handle does (ekf_params.hpp).
+// launch's parameter block as the handle does (ekf_params.hpp); derive, inputs_view and check_run are side_run_host.hpp's.
 #include "../../include/qle_score.h"
 
 #include "ekf_params.hpp"
 #include "ekf_score.hpp"
-#include "side_host.hpp"
+#include "side_run_host.hpp"
 
 using namespace qle;
 using namespace qle::side;
@@ -41,16 +41,6 @@ static int check_tick(const qle_device_view* v, const qle_inputs_view* in, const
     if (v->num_states != (p->est_bias ? 15 : 9)) return fail(QLE_ERR_INVALID, "view: num_states %d, params: est_bias %d", v->num_states, p->est_bias);
     return QLE_OK;
 }
-static int derive(const qle_params* p, qle_derived* der)
-{
-    return qle_params_derive(p, der) == QLE_OK ? QLE_OK : fail(QLE_ERR_INVALID, "params: %s", qle_last_error());
-}
-static int inputs_view(const qle_inputs* in, int64_t t, qle_inputs_view* iv)
-{
-    iv->struct_size = sizeof(qle_inputs_view);
-    const int rc = qle_inputs_get_device_view(in, t, iv);
-    return rc == QLE_OK ? QLE_OK : fail(rc, "%s", qle_last_error());
-}
 
 template <typename T>
 static int launch_t(const qle_device_view* v, const qle_inputs_view* in, const qle_params& pub, const qle_derived& der, double* acc)
@@ -82,22 +72,6 @@ extern "C" int qsc_score_tick(const qle_device_view* view, const qle_inputs_view
 }
 
 // ---- qsc_run
-// The handle's view and [t0, t0 + n) inside the sequence (the tick library is the one that knows its length, and says so without a
-// GPU call); no GPU call.
-static int check_run(qle_batch* h, const qle_inputs* in, int64_t t0, int64_t n, const qle_params* p, qle_device_view* v)
-{
-    if (!h) return fail(QLE_ERR_INVALID, "handle is null");
-    if (!in) return fail(QLE_ERR_INVALID, "inputs is null");
-    v->struct_size = sizeof(*v);
-    if (int rc = qle_get_device_view(h, v)) return fail(rc, "%s", qle_last_error());
-    QLE_TRY(check_view(v, ViewSize::at_least, false));
-    if (v->num_states != (p->est_bias ? 15 : 9)) return fail(QLE_ERR_INVALID, "handle: num_states %d, params: est_bias %d", v->num_states, p->est_bias);
-    if (t0 < 0 || n < 0) return fail(QLE_ERR_INVALID, "t0 and n must be >= 0 (got %lld, %lld)", (long long)t0, (long long)n);
-    qle_inputs_view iv;
-    if (n > 0 && (inputs_view(in, t0, &iv) != QLE_OK || inputs_view(in, t0 + n - 1, &iv) != QLE_OK))
-        return fail(QLE_ERR_INVALID, "ticks [%lld, %lld) reach beyond the sequence: %s", (long long)t0, (long long)(t0 + n), qle_last_error());
-    return QLE_OK;
-}
 // behind every refusal and use_device
 static int run_loop(qle_batch* h, const qle_device_view* v, const qle_inputs* in, int64_t t0, int64_t n, const qle_params& pub, const qle_derived& der, double* acc)
 {

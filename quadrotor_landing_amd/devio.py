@@ -43,6 +43,10 @@ modes with recursive mode probabilities `logmu`, and the mixing step that re-ini
 its bank, in place, in one launch; `Imm.step(u, z, mask)` runs the cycle mix, score, tick, update around one tick and `Imm.fuse()` is
 `bank(M).fuse(logmu)`.
 
+Adaptive tag-pose noise (adapt.py, libqle_adapt.so): `adapter(window, gain, ...)` returns an `Adapter` whose `step(u, z, mask)` in place of
+`tick`, or `run(seq)` in place of `run`, lets every filter estimate its own R_r / R_ang from its innovations -- one read-only launch per
+tag tick, one launch per window that writes the six R words of the per-filter parameter records, the ticks themselves unchanged.
+
 Still host-fed through `BatchedRelativePoseEKF`: `set_state` and the per-filter stamps of `dynamic_meas_delay`
 (`filter_update(t_curr=..., apriltag_time=...)`).
 """
@@ -50,6 +54,7 @@ import ctypes as C
 import math
 
 from . import _tensors as _t
+from . import adapt as _adapt
 from . import bank as _bank
 from . import gate as _gate
 from . import health as _health
@@ -248,6 +253,19 @@ class DeviceIO(DeviceRecords):
         `result()` / `summary()` read them as per-filter log-likelihood and innovation consistency statistics.  Refused with
         multirate_ekf."""
         return _score.Scorer(self)
+
+    # ---- adaptive tag-pose noise
+    def adapter(self, window=20, gain=1.0, n_min=None, chi2_max=float("inf"), R_lo=None, R_hi=None):
+        """An `adapt.Adapter` for this handle: every filter estimates its diagonal tag-pose noise R from its own innovations.
+        `observe(u, z, mask)` in front of a `tick` adds a noise sample per component of R to fp64 accumulators on the GPU (ONE read-only
+        launch, k_adapt_observe); `apply()` moves R towards the window's mean sample, R_k <- clamp(R_k + gain (mean - R_k), R_lo[k],
+        R_hi[k]), for every filter that scored at least n_min ticks (None: window // 2) and writes words 18..23 of its parameter record
+        (ONE launch, k_adapt_apply); `step(u, z, mask)` is observe, tick and an apply after every window-th tag tick; `run(seq)` is
+        the sequence form.  chi2_max: tag ticks with NIS above it are not scored (inf: no limit; the tick still applies them).  Bounds
+        default to the shared R / 100 and x 100.  Puts per-filter parameters in force when they are not (one host upload, here only).
+        The estimate is the R under which the filter's own model explains its innovations, not the sensor's noise wherever the model is
+        off.  Refused with multirate_ekf."""
+        return _adapt.Adapter(self, window, gain, n_min, chi2_max, R_lo, R_hi)
 
     # ---- look-ahead: state and covariance h ticks ahead, read-only
     def lookahead(self, u, h, mask=None, sigma_r_max=float("inf"), sigma_theta_max=float("inf")):

@@ -351,6 +351,19 @@ class BatchedRelativePoseEKF:
         return {"acc": acc, "n": s.n, "n_bad": s.n_bad, "nis_mean": s.nis_mean, "loglik": s.loglik, "var_ratio": s.var_ratio, "rho1": s.rho1,
                 "nu_mean": s.nu_mean}
 
+    def adapt_noise(self, inputs, t0, n, **cfg):
+        """Ticks [t0, t0 + n) of `inputs`, with every filter's tag-pose noise R adapted from its innovations on the device: what
+        `DeviceIO.adapter(**cfg).run` does (cfg: window, gain, n_min, chi2_max, R_lo, R_hi), for host arrays.  Puts per-filter
+        parameters in force when they are not.  Returns a dict of numpy arrays: acc [24,B] (the accumulator words of
+        include/qle_adapt.h), R [B,6] (the values in force after the run) and the fields of `adapt.Adaptation` -- n, n_bad, n_rejected,
+        n_total, windows [B], r_hat, ratio [B,6].  Refused with multirate_ekf."""
+        from . import adapt as ad
+        acc, R = ad.run_host(self, inputs, t0, n, **cfg)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a = ad.Adaptation(acc)
+        return {"acc": acc, "R": R, "n": a.n, "n_bad": a.n_bad, "n_rejected": a.n_rejected, "n_total": a.n_total, "windows": a.windows,
+                "r_hat": a.r_hat, "ratio": a.ratio}
+
     # ---- filter health
     def health(self, mask=None, sigma_r_max=float("inf"), sigma_v_max=float("inf"), sigma_theta_max=float("inf"), qnorm_tol=1e-3, select=None):
         """Which filters are broken?  Host arrays in and out; the classification runs on the device (k_health), the state is unchanged.
