@@ -18,7 +18,7 @@ import math
 from . import _tensors as _t
 from . import gate as _gate
 from ._lib import QleDeviceView, QleInputsView, QleParams, SideLibrary
-from .sequence import DeviceSequence
+from ._observer import TagTickObserver
 
 WORDS = 24   # QAD_WORDS
 # the words of an accumulator record: name -> (first word, count)
@@ -106,24 +106,22 @@ class Adaptation:
         self.ratio = (w("sum_a_sq") / w("sum_c")).T
 
 
-class Adapter:
+class Adapter(TagTickObserver):
     """Noise adaptation of a handle fed from device tensors (`DeviceIO.adapter()`).  Owns a zeroed accumulator tensor `acc`
     [WORDS, padded batch] (float64, include/qle_adapt.h) on the handle's GPU and the configuration `cfg`.  Puts per-filter parameters
     in force when they are not (the shared record replicated: a host upload, at construction only); after that every call is
     asynchronous and none synchronises.  `ekf.get_filter_params()` reads the adapted R back (words 18..23)."""
+    LIB, WORDS, WHAT, RESULT = ADAPT, WORDS, "noise adaptation", Adaptation
 
     def __init__(self, io, window=20, gain=1.0, n_min=None, chi2_max=float("inf"), R_lo=None, R_hi=None):
-        _gate.refuse_multirate(io.ekf.params, "noise adaptation")
-        self.io = io
+        super().__init__(io)
         self.cfg = make_config(io.ekf, window, gain, n_min, chi2_max, R_lo, R_hi)
         _in_force(io.ekf)
-        self._Bp = -(-io.ekf.batch // 64) * 64
-        self.acc = _t.empty(io.ekf.device, (WORDS, self._Bp), "float64", zero=True)
         self._tags = 0   # tag ticks `step` has taken since the last reset: the window counter, kept on the host
 
     def reset(self):
         """Zero the accumulators and the window counter of `step`; the adapted R stays in the parameter records."""
-        self.acc.zero_()
+        super().reset()
         self._tags = 0
 
     def observe(self, u, z, mask=None):
@@ -131,19 +129,10 @@ class Adapter:
         mask [B] (uint8 / bool; None = all) into the slot the tick will pack again, and adds every filter's noise sample, taken
         against the predicted state, to its accumulators.  One pack and ONE launch of k_adapt_observe; neither the state nor the
         parameter records are touched."""
-        io = self.io
-        B = io.ekf.batch
-        src = io._check(u, "u", (B, 6))
-        if io._check(z, "z", (B, 7)) != src:
-            raise ValueError("u and z must have the same dtype")
-        io._check_mask(mask)
-        D, Q = _t.devio_lib(), adapt_lib()
-        view = io._view()
-        iv = io._inputs_view(1)
-        with io._ordered(view, u, z, mask, self.acc):
-            _t.dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), u.data_ptr(), z.data_ptr(), None if mask is None else mask.data_ptr(),
-                                        _t.FLOATS[src]))
-            qcheck(Q.qad_observe_tick(C.byref(view), C.byref(iv), C.byref(io.ekf.params), self.acc.data_ptr(), self.cfg.chi2_max))
+        super().observe(u, z, mask)
+
+    def _observe_tick(self, Q, view, iv):
+        return Q.qad_observe_tick(C.byref(view), C.byref(iv), C.byref(self.io.ekf.params), self.acc.data_ptr(), self.cfg.chi2_max)
 
     def apply(self):
         """The M-step: every filter with n >= n_min gets R_k <- clamp(R_k + gain (sum r^_k / n - R_k), R_lo[k], R_hi[k]) written into
@@ -176,16 +165,14 @@ class Adapter:
         """Ticks [t0, t0 + n) of a `DeviceSequence` (n None: to its end), adapted, in ONE native call (qad_run): k_adapt_observe in front
         of every tick that has a tag slot, the tick, and k_adapt_apply after every window-th tag-slot tick, counted from the start of
         this call -- the bits of the loop of `step` over the same ticks after a `reset`."""
-        io = self.io
-        t0, n = DeviceSequence.window(io, seq, t0, n)
-        Q = adapt_lib()
-        view = io._view()
-        with io._ordered(view, self.acc):
-            qcheck(Q.qad_run(io.ekf._h, seq.inputs._h, t0, n, C.byref(io.ekf.params), self.acc.data_ptr(), C.byref(self.cfg)))
+        super().run(seq, t0, n)
+
+    def _run(self, Q, seq, t0, n):
+        return Q.qad_run(self.io.ekf._h, seq.inputs._h, t0, n, C.byref(self.io.ekf.params), self.acc.data_ptr(), C.byref(self.cfg))
 
     def result(self):
         """The accumulators as an `Adaptation` of device tensors [B] / [B,6]; no synchronisation."""
-        return Adaptation(self.acc[:, :self.io.ekf.batch])
+        return super().result()
 
 
 def run_host(ekf, inputs, t0, n, **cfg):

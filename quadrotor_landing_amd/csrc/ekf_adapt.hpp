@@ -173,9 +173,6 @@ __host__ __device__ __forceinline__ bool adapt_apply_one(const AdaptApplyCfg& cf
 
 namespace qle {
 
-static_assert(pregate_cov_words<4, false, true> == 120 && pregate_cov_words<2, false, true> == 90 && pregate_cov_words<4, true, true> == 48 &&
-              pregate_cov_words<2, true, true> == 46, "the covariance words in the counts stated at the top of this file");
-
 // One lane per filter, one wave per workgroup (a workgroup is one 64-filter tile).  Reads the state, the tick's records and the
 // parameter record, writes none of them.  acc [kAdaptWords][Bp] doubles, Bp = the padded batch (gridDim.x * kTile): every lane may load
 // its record.  One wave per SIMD is what the registers are budgeted for, as for k_score and for its reason: the record is 46 registers

@@ -1,13 +1,12 @@
 // gate_capi.hip -- C ABI of include/qle_gate.h over ekf_pregate.hpp.  Host side: argument checks (every refusal before any GPU call)
 // and ONE launch on the view's stream.  Works from the view structs of include/qle_ekf.h and the public parameters; links
-// libqle_ekf.so for qle_params_derive and derives the launch's parameter block as the handle does (ekf_params.hpp).
+// libqle_ekf.so for qle_params_derive; derive and the launch ladder are side_run_host.hpp's.
 #include "../../include/qle_gate.h"
 
 #include <cmath>
 
-#include "ekf_params.hpp"
 #include "ekf_pregate.hpp"
-#include "side_host.hpp"
+#include "side_run_host.hpp"
 
 using namespace qle;
 using namespace qle::side;
@@ -37,14 +36,10 @@ struct Outs { void* nis; uint8_t* accepted; void* nu; void* S; int32_t f64; doub
 template <typename T, bool PREDICT>
 static int launch_t(const qle_device_view* v, const qle_inputs_view* in, const qle_params& pub, const qle_derived& der, const Outs& o)
 {
-    DevParams<T> dp = make_dev<T>(pub, der);
-    dp.compact = v->compact ? 1 : 0;
-    auto go = [&](auto direct, auto pfp, auto compact) {
+    return launch_flags<T>(v, pub, der, [&](const DevParams<T>& dp, auto direct, auto pfp, auto compact) {
         hipLaunchKernelGGL((k_pregate<T, decltype(direct)::value, decltype(pfp)::value, decltype(compact)::value, PREDICT>), tiles(v), dim3(kTile), 0, stream_of(v),
                            (const T*)v->state, (const T*)in->u, (T*)in->z, v->batch, (const T*)v->filter_params, o.nis, o.accepted, o.nu, o.S, o.f64, o.chi2_max, dp);
-    };
-    with(pub.direct_orien_method != 0, [&](auto d) { with(v->filter_params != nullptr, [&](auto f) { with(v->compact != 0, [&](auto c) { go(d, f, c); }); }); });
-    return launched();
+    });
 }
 
 template <bool PREDICT>
@@ -52,7 +47,7 @@ static int run(const qle_device_view* v, const qle_inputs_view* in, const qle_pa
 {
     QLE_TRY(check_args(v, in, p, PREDICT, o.chi2_max, o.f64));
     qle_derived der;
-    if (qle_params_derive(p, &der) != QLE_OK) return fail(QLE_ERR_INVALID, "params: %s", qle_last_error());
+    QLE_TRY(derive(p, &der));
     if (!PREDICT && !o.nis && !o.nu && !o.S) return QLE_OK;
     QLE_TRY(use_device(v));
     return v->dtype == QLE_F32 ? launch_t<float, PREDICT>(v, in, *p, der, o) : launch_t<double, PREDICT>(v, in, *p, der, o);

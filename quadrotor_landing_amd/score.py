@@ -10,10 +10,9 @@ is an error.
 import ctypes as C
 import math
 
-from . import _tensors as _t
 from . import gate as _gate
 from ._lib import QleDeviceView, QleInputsView, QleParams, SideLibrary
-from .sequence import DeviceSequence
+from ._observer import TagTickObserver
 
 WORDS, SUMS = 40, 30   # QSC_WORDS, QSC_SUMS
 # the words of an accumulator record: name -> (first word, count)
@@ -56,52 +55,31 @@ class Score:
         self.nu_mean = (w("sum_nu") / n).T
 
 
-class Scorer:
+class Scorer(TagTickObserver):
     """Innovation scoring of a handle fed from device tensors (`DeviceIO.scorer()`).  Owns a zeroed accumulator tensor `acc`
     [WORDS, padded batch] (float64, include/qle_score.h) on the handle's GPU.  Every call is asynchronous and none synchronises."""
-
-    def __init__(self, io):
-        _gate.refuse_multirate(io.ekf.params, "scoring")
-        self.io = io
-        self._Bp = -(-io.ekf.batch // 64) * 64
-        self.acc = _t.empty(io.ekf.device, (WORDS, self._Bp), "float64", zero=True)
-
-    def reset(self):
-        self.acc.zero_()
+    LIB, WORDS, WHAT, RESULT, RECHECK = SCORE, WORDS, "scoring", Score, True
 
     def observe(self, u, z, mask=None):
         """Score the tag poses of the tick `io.tick(u, z, mask)` is about to run -- call it BEFORE that tick: packs u [B,6], z [B,7] and
         mask [B] (uint8 / bool; None = all) into the slot the tick will pack again, and adds every filter's innovation against the
         predicted state to its accumulators.  One pack and ONE launch of k_score; the state is not touched."""
-        io = self.io
-        B = io.ekf.batch
-        src = io._check(u, "u", (B, 6))
-        if io._check(z, "z", (B, 7)) != src:
-            raise ValueError("u and z must have the same dtype")
-        io._check_mask(mask)
-        _gate.refuse_multirate(io.ekf.params, "scoring")
-        D, Q = _t.devio_lib(), score_lib()
-        view = io._view()
-        iv = io._inputs_view(1)
-        with io._ordered(view, u, z, mask, self.acc):
-            _t.dcheck(D.qdv_pack_inputs(C.byref(view), C.byref(iv), u.data_ptr(), z.data_ptr(), None if mask is None else mask.data_ptr(),
-                                        _t.FLOATS[src]))
-            qcheck(Q.qsc_score_tick(C.byref(view), C.byref(iv), C.byref(io.ekf.params), self.acc.data_ptr()))
+        super().observe(u, z, mask)
+
+    def _observe_tick(self, Q, view, iv):
+        return Q.qsc_score_tick(C.byref(view), C.byref(iv), C.byref(self.io.ekf.params), self.acc.data_ptr())
 
     def run(self, seq, t0=0, n=None):
         """Ticks [t0, t0 + n) of a `DeviceSequence` (n None: to its end), scored, in ONE native call (qsc_run): what `io.run(seq, t0, n)`
         does -- state and sequence end with its bits -- with k_score in front of every tick that has a tag slot."""
-        io = self.io
-        t0, n = DeviceSequence.window(io, seq, t0, n)
-        _gate.refuse_multirate(io.ekf.params, "scoring")
-        Q = score_lib()
-        view = io._view()
-        with io._ordered(view, self.acc):
-            qcheck(Q.qsc_run(io.ekf._h, seq.inputs._h, t0, n, C.byref(io.ekf.params), self.acc.data_ptr()))
+        super().run(seq, t0, n)
+
+    def _run(self, Q, seq, t0, n):
+        return Q.qsc_run(self.io.ekf._h, seq.inputs._h, t0, n, C.byref(self.io.ekf.params), self.acc.data_ptr())
 
     def result(self):
         """The accumulators as a `Score` of device tensors [B] / [B,6]; no synchronisation."""
-        return Score(self.acc[:, :self.io.ekf.batch])
+        return super().result()
 
     def summary(self, mask=None):
         """Words 0..29 of the accumulators added over the filters with mask != 0 (uint8 / bool [B]; None = all): a float64 device tensor

@@ -23,7 +23,7 @@ import host_harness
 import oracle
 from adapt_util import APPLY_TOL, COUNTS, TOL, apply_error, apply_ref, deviations, reference_run
 from elf_util import _kernels
-from gate_util import HW, TOL as GATE_TOL
+from gate_util import HW, TOL as GATE_TOL, predict_then_innovation
 from innovation_util import CHI2_6_099
 from oracle import ekf_np
 from quadrotor_landing_amd import _lib, adapt
@@ -300,3 +300,27 @@ def test_host_compiled_arithmetic_adapts_over_six_ticks_as_the_reference(harness
         print(f"{dtype} direct={direct}: " + " ".join(f"{g} {v:.2e}" for g, v in worst.items()))
         tol = TOL["cpu"][dtype]
         assert all(worst[g] < tol[g] for g in worst), (worst, tol)
+
+
+def test_a_tick_whose_S_is_not_positive_definite_counts_in_n_bad_and_changes_no_other_word(harness, tmp_path):
+    """One tag tick, fp64: every fourth filter holds a negated covariance, so its S is finite with a negative eigenvalue.  Such a
+    tick counts in n_bad and moves neither another word of the record nor R, whichever of the source's two factorisations of S
+    (pregate_eval_pivots, adapt_sample) says so: both see the same S.  The other filters score the tick."""
+    po = oracle.make_params(update_freq=400.0, direct_orien_method=1, est_bias=1, **HW)
+    p = ekf_np.Params.from_orc(po)
+    rng = np.random.default_rng(41)
+    x, P = rand_states(rng, NF, po.num_states, cov_scale=0.05)
+    pfp = np.tile(np.array([*po.Q, *HW["ab_static"], *HW["wb_static"], *po.R]), (NF, 1))
+    U, Z = make_sequence(rng, po, x, P, 1, range(1), pfp, ang=0.05, pos=0.03)
+    bad = np.arange(NF) % 4 == 1
+    P[bad] = -P[bad]
+    _, S, _, _, _ = predict_then_innovation(po, p, x, P, U[0], Z[0], pfp)
+    low = np.linalg.eigvalsh(S).min(axis=1)
+    assert np.isfinite(S).all() and (low[bad] < 0).all() and (low[~bad] > 0).all()
+    per = [np.concatenate([x, host_harness.full_P(P), U[0], Z[0], pfp, np.ones((NF, 1))], axis=1)]
+    for exe in harness:
+        out = host_harness.run(exe, tmp_path, _header(po, "f64", 1, window=2), per, (NF, 30))   # one tick of a window of two: no apply
+        acc, R_end = out[:, :24], out[:, 24:30]
+        assert (acc[bad, 1] == 1).all() and not np.delete(acc[bad], 1, axis=1).any()
+        assert (acc[~bad, 0] == 1).all() and (acc[~bad, 20] == 1).all() and not acc[~bad][:, [1, 22]].any()
+        np.testing.assert_array_equal(R_end, pfp[:, 18:24])
