@@ -21,8 +21,9 @@
  *     path of qle_ekf.h gives for the same values ((T)double in, (double)T out; float32 out = (float) of that double).
  *   - every call returns 0 or a negative error class of qle_ekf.h (QLE_ERR_*); the message is in qdv_last_error()
  *     (thread-local).
- *   - out of scope, still host-fed through qle_ekf.h: qle_set_state and the per-filter stamps of dynamic_meas_delay
- *     (qle_filter_update_stamped).  The NIS-gated tick from device tensors lives in include/qle_gate.h (libqle_gate.so):
+ *   - out of scope, still host-fed through qle_ekf.h: the per-filter stamps of dynamic_meas_delay
+ *     (qle_filter_update_stamped).  Writing the state from device tensors -- qle_set_state without the host, snapshot, restore,
+ *     gather -- lives in include/qle_stateio.h (libqle_stateio.so).  The NIS-gated tick from device tensors lives in include/qle_gate.h (libqle_gate.so):
  *     one launch between qdv_pack_inputs and qle_run.  Seeding from device tensors is qdv_pack_inputs into a tag slot
  *     followed by qle_initialize_state_slot (qle_ekf.h); health check and retirement live in include/qle_health.h.
  */

@@ -140,6 +140,12 @@ int32_t qle_num_states(const qle_batch *h);
 /* Write r_nom,v_nom,q_nom,ab_nom,wb_nom and cov_pert (EKF.hpp:47-53) for all
  * filters.  x = [batch][16]; P = [batch][n][n] (symmetrised as (P+P^T)/2). */
 int qle_set_state(qle_batch *h, const double *x, const double *P);
+/* The caller has written state records through the device view (qle_get_device_view) on the handle's stream; treat it as
+ * qle_set_state: the handle has a state from now on, a handle with gating that had none starts every filter's
+ * upds_since_correction at 0 (one that had a state keeps its counters), and a multirate history restarts at the next tick, for
+ * every filter.  This is what qle_set_state does once its arrays are staged; include/qle_stateio.h is the caller (state from
+ * device tensors, restore of a snapshot, gather).  Launches no kernel but the counter fill of that first state. */
+int qle_mark_state_written(qle_batch *h);
 /* Read them back (NODE.cpp:195-220 reads these members after a tick). */
 int qle_get_state(qle_batch *h, double *x, double *P);
 /* RelativePoseEKF::initialize_state(reinit_bias), EKF.cpp:305-344, batched:

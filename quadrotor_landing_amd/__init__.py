@@ -14,4 +14,5 @@ from . import imm  # noqa: F401
 from . import lookahead  # noqa: F401
 from . import score  # noqa: F401
 from . import sequence  # noqa: F401
+from . import stateio  # noqa: F401
 from .sequence import DeviceSequence, SequenceResult  # noqa: F401

@@ -107,6 +107,7 @@ SYMBOLS = {
     "qle_num_states": (_i32, [_vp]),
     "qle_set_state": (C.c_int, [_vp, _pd, _pd]),
     "qle_get_state": (C.c_int, [_vp, _pd, _pd]),
+    "qle_mark_state_written": (C.c_int, [_vp]),
     "qle_initialize_state": (C.c_int, [_vp, _pd, _i32]),
     "qle_initialize_state_masked": (C.c_int, [_vp, _pd, _pu8, _i32]),
     "qle_initialize_state_slot": (C.c_int, [_vp, _vp, _i64, _i32]),
@@ -180,7 +181,7 @@ def check(rc):
 
 
 class SideLibrary:
-    """One of the libraries beside libqle_ekf.so (devio, gate, consistency, health, lookahead, sequence, score, bank, imm, adapt): where it is
+    """One of the libraries beside libqle_ekf.so (devio, gate, consistency, health, lookahead, sequence, score, bank, imm, adapt, stateio): where it is
     (`env` names the environment variable that overrides the in-tree path), what it exports (`symbols`, name -> (restype, argtypes)),
     `what` it is for (the error text when it is missing), the name of its `*_last_error`, and what has to be loaded in front of it.
     needs_tick_library: the library takes qle_params_derive from the tick library, which is loaded first so that it is the same copy

@@ -504,6 +504,13 @@ extern "C" int qle_set_state(qle_batch* h, const double* x, const double* P)
     if (!x || !P) return fail(QLE_ERR_INVALID, "x and P must be non-null");
     QLE_TRY(BY_DTYPE(h, stage_rows, h, x, kXW, kXW, state_cur(h), kSW, 0));
     QLE_TRY(BY_DTYPE(h, stage_P, h, P, state_cur(h)));
+    return qle_mark_state_written(h);
+}
+// What a written state means to the handle's host flags; host only but for the fill of a fresh gating handle's counters.  The tail of
+// qle_set_state, and the whole of it for a caller that wrote the records itself through the device view (include/qle_stateio.h).
+extern "C" int qle_mark_state_written(qle_batch* h)
+{
+    QLE_TRY(check_handle(h));
     if (!h->state_set && h->last_corr) {   // first state of the handle: upds_since_correction = 0 now (EKF.cpp:77)
         QLE_TRY(seed_prev_tick(h, h->last_corr));
     }

@@ -1,4 +1,4 @@
-// side_host.hpp -- the host scaffold the side libraries share (devio, gate, consistency, health, lookahead, sequence, score, bank, imm, adapt: csrc/Makefile, SIDE).
+// side_host.hpp -- the host scaffold the side libraries share (devio, gate, consistency, health, lookahead, sequence, score, bank, imm, adapt, stateio: csrc/Makefile, SIDE).
 // Host code only, every symbol internal: a library that includes it has an error string and a launch counter of its own, and
 // exports nothing it did not export before.  A *_capi.hip file keeps its static_asserts, the refusals that are its own, its launches
 // and its extern "C" entries; what every one of them needs around those is here.

@@ -47,7 +47,13 @@ Adaptive tag-pose noise (adapt.py, libqle_adapt.so): `adapter(window, gain, ...)
 `tick`, or `run(seq)` in place of `run`, lets every filter estimate its own R_r / R_ang from its innovations -- one read-only launch per
 tag tick, one launch per window that writes the six R words of the per-filter parameter records, the ticks themselves unchanged.
 
-Still host-fed through `BatchedRelativePoseEKF`: `set_state` and the per-filter stamps of `dynamic_meas_delay`
+Device state I/O (stateio.py, libqle_stateio.so): `set_state(x, P, mask)` writes the state from device tensors, one launch, the bits of
+the host `set_state`; `snapshot()` returns a `Snapshot` -- a bitwise copy of the records in a workspace of its own, readable through the
+same calls (`state`, `report`, `health`, `nees`, `lookahead`); `restore(snap, mask, index)` writes it back, into this handle or another
+of the same dtype and layout; `gather(index)` permutes or resamples the filters in place and `fork(members)` starts every member of a
+bank from one filter.  A snapshot holds the state, not the multirate history and not the counters.
+
+Still host-fed through `BatchedRelativePoseEKF`: the per-filter stamps of `dynamic_meas_delay`
 (`filter_update(t_curr=..., apriltag_time=...)`).
 """
 import ctypes as C
@@ -62,6 +68,7 @@ from . import imm as _imm
 from . import lookahead as _look
 from . import score as _score
 from . import sequence as _seqm
+from . import stateio as _sio
 from ._lib import QleInputsView, check, lib
 from ._tensors import DEVIO, QDV_F32, QDV_F64, SYMBOLS, devio_lib  # noqa: F401
 from .records import DeviceRecords
@@ -77,6 +84,7 @@ class DeviceIO(DeviceRecords):
         super().__init__(ekf, ekf.batch)
         self._seq = None   # two ticks: 0 without a tag slot, 1 with one (made on the first tick)
         self._zero_u = {}  # innovation(): an all-zero IMU tensor per source dtype for the pack
+        self._gather_snap = None   # gather(): the snapshot an in-place permutation goes through (made on the first gather)
 
     def _view(self):
         return _t.device_view(self.ekf)
@@ -297,7 +305,48 @@ class DeviceIO(DeviceRecords):
         `bank(members).fuse(logmu, mask)`; `mu()` the normalised probabilities.  Refused with multirate_ekf."""
         return _imm.Imm(self, members, Pi, logmu0, logmu_min)
 
+    # ---- device state I/O: set_state from tensors, snapshot, restore, gather, fork
+    def set_state(self, x, P=None, mask=None):
+        """`set_state(x, P)` of the host path from device tensors: x [B,16] and P [B,n,n] (float32 or float64, alike) become the state
+        records in ONE launch (k_si_pack), bit for bit what `qle_set_state` writes for the same values -- (P + P^T) / 2 formed in
+        double, then the cast to the compute dtype.  Either may be None: that part of every record is kept.  Filters with mask 0
+        (uint8 / bool; None = all) keep their records.  Works on a handle that was never given a state from the host.  As after the
+        host call, a multirate history restarts at the next tick and the counters of `enable_gating` go on (a handle without a state
+        starts them at 0); with multirate_ekf a mask is refused, because that restart is every filter's.  Asynchronous; the tensors
+        may be reused as soon as the call returns."""
+        _sio.set_state(self, x, P, mask)
+
+    def snapshot(self, with_params=False):
+        """A checkpoint: a `stateio.Snapshot` that owns a bitwise copy of every filter's record (ONE launch of k_si_copy into a
+        workspace of its own; with_params=True: of the per-filter parameter records too) and offers `state()`, `report()`,
+        `health(...)`, `nees(...)` and `lookahead(...)` on it.  The handle is not written.  A snapshot is the state at this tick:
+        it holds neither the multirate history nor the counters (upds_since_correction, the rate limiter)."""
+        return _sio.snapshot(self, with_params)
+
+    def restore(self, snap, mask=None, index=None, with_params=False):
+        """Write a snapshot back in ONE launch: filter i becomes a bitwise copy of the snapshot's filter index[i] (index: an int32
+        device tensor [B]; None = i), for the filters with mask != 0 (None = all) whose index is inside the snapshot.  With an index
+        returns `written` [B] (uint8): 0 where mask or index left a filter as it was.  snap may be another `DeviceIO`'s, of the same
+        dtype, layout and device -- with an index of any batch size; the two handles' streams are ordered here.  with_params=True:
+        the parameter records of a snapshot taken `with_params` travel too.  NaN words and all-zero ("uninitialised") records
+        arrive as they are: restoring a retired filter retires the destination.  Then as `set_state`: the history restarts, the
+        counters go on, a mask is refused with multirate_ekf."""
+        return _sio.restore(self, snap, mask, index, with_params)
+
+    def gather(self, index, mask=None):
+        """In place: filter i becomes filter index[i] (a permutation, a resampling step, duplicates welcome) -- a snapshot into a
+        workspace this object keeps, then `restore(snapshot, mask, index)`: two launches.  Returns `written` [B].  The per-filter
+        parameter records stay where they are."""
+        return _sio.gather(self, index, mask)
+
+    def fork(self, members, source=0):
+        """Every filter becomes a copy of member `source` of its bank of `members` consecutive filters: `gather` with
+        index[i] = (i // members) * members + source.  The per-filter parameter records are not copied: they are what tells a bank's
+        members apart (`bank`, `imm`)."""
+        return _sio.gather(self, _sio.fork_index(self, members, source))
+
     def close(self):
+        self._gather_snap = None
         if self._seq is not None:
             self._seq.close()
             self._seq = None

@@ -148,6 +148,14 @@ class BatchedRelativePoseEKF:
         check(lib().qle_get_state(self._h, _dp(x), _dp(P)))
         return x, P
 
+    def gather_state(self, index, mask=None):
+        """In place, on the device: filter i becomes a bitwise copy of filter index[i] (int32 [B]; a permutation, a resampling step,
+        the members of a bank forked from one filter) for the filters with mask != 0 (None = all) whose index is in 0..B-1 -- what
+        `DeviceIO.gather` does, for host arrays: the state never passes through the host.  Returns `written` [B] (uint8).  Then as
+        `set_state`: a multirate history restarts at the next tick (a mask is refused with multirate_ekf), the counters go on."""
+        from . import stateio as sio
+        return sio.gather_host(self, index, mask)
+
     def initialize_state(self, z, reinit_bias=False, mask=None):
         """RelativePoseEKF::initialize_state (relative_pose_EKF.cpp:305-344) from each filter's first tag pose.
         mask [batch]: seed only those filters (the node seeds a filter on its own first detection,
