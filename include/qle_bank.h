@@ -54,6 +54,11 @@ extern "C" {
 const char *qbk_last_error(void);
 /* Diagnostics: kernel launches this library has made in this process so far (all threads). */
 int64_t qbk_launch_count(void);
+/* Diagnostics: the launch census of this library, the contract of qle_launch_census_begin / _end (qle_ekf.h): the distinct
+ * kernels this library has launched since begin, process-wide; end stops the census and writes their mangled names, sorted,
+ * each followed by '\n', by the two-call size protocol.  Off, the census costs one relaxed atomic load per launch. */
+int qbk_launch_census_begin(void);
+int qbk_launch_census_end(char *names, int64_t cap, int64_t *needed);
 
 /* Bytes of the workspace the fused records of this view need (state_words words of the compute dtype for padded(batch /
  * members) filters), or a negative error class. */

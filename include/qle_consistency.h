@@ -65,6 +65,11 @@ typedef struct qcs_summary {
 const char *qcs_last_error(void);
 /* Diagnostics: kernel launches this library has made in this process so far (all threads). */
 int64_t qcs_launch_count(void);
+/* Diagnostics: the launch census of this library, the contract of qle_launch_census_begin / _end (qle_ekf.h): the distinct
+ * kernels this library has launched since begin, process-wide; end stops the census and writes their mangled names, sorted,
+ * each followed by '\n', by the two-call size protocol.  Off, the census costs one relaxed atomic load per launch. */
+int qcs_launch_census_begin(void);
+int qcs_launch_census_end(char *names, int64_t cap, int64_t *needed);
 
 /* NEES of every filter of the view against x_true.  nees, err and summary may each be NULL.  chi2_hi > 0 is the bound
  * n_above counts against; +INFINITY gives 0.  With a summary: TWO launches (k_nees, k_nees_reduce) and a partials buffer

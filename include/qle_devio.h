@@ -40,6 +40,11 @@ extern "C" {
 #define QDV_F64 1
 
 const char *qdv_last_error(void);
+/* Diagnostics: the launch census of this library, the contract of qle_launch_census_begin / _end (qle_ekf.h): the distinct
+ * kernels this library has launched since begin, process-wide; end stops the census and writes their mangled names, sorted,
+ * each followed by '\n', by the two-call size protocol.  Off, the census costs one relaxed atomic load per launch. */
+int qdv_launch_census_begin(void);
+int qdv_launch_census_end(char *names, int64_t cap, int64_t *needed);
 
 /* u = [batch][6] (accel, gyro) -> the IMU records of the tick `in` describes; when that tick has a tag slot also
  * z = [batch][7] (NULL = identity pose) and mask = [batch] (NULL = all set) -> its tag records, as qle_inputs_upload_tick

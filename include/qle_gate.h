@@ -59,6 +59,11 @@ int qgt_innovation(const qle_device_view *view, const qle_inputs_view *in, const
                    void *S, int32_t dst_dtype);
 /* Diagnostics: kernel launches this library has made in this process so far (all threads). */
 int64_t qgt_launch_count(void);
+/* Diagnostics: the launch census of this library, the contract of qle_launch_census_begin / _end (qle_ekf.h): the distinct
+ * kernels this library has launched since begin, process-wide; end stops the census and writes their mangled names, sorted,
+ * each followed by '\n', by the two-call size protocol.  Off, the census costs one relaxed atomic load per launch. */
+int qgt_launch_census_begin(void);
+int qgt_launch_census_end(char *names, int64_t cap, int64_t *needed);
 
 #ifdef __cplusplus
 }

@@ -75,6 +75,11 @@ typedef struct qhl_summary {
 const char *qhl_last_error(void);
 /* Diagnostics: kernel launches this library has made in this process so far (all threads). */
 int64_t qhl_launch_count(void);
+/* Diagnostics: the launch census of this library, the contract of qle_launch_census_begin / _end (qle_ekf.h): the distinct
+ * kernels this library has launched since begin, process-wide; end stops the census and writes their mangled names, sorted,
+ * each followed by '\n', by the two-call size protocol.  Off, the census costs one relaxed atomic load per launch. */
+int qhl_launch_census_begin(void);
+int qhl_launch_census_end(char *names, int64_t cap, int64_t *needed);
 
 /* Classify every filter of the view.  mask = [batch] bytes or NULL (all); status, flagged and summary may each be NULL.
  * Changes nothing in the handle.  With a summary: TWO launches (k_health, k_health_reduce) and a partials buffer the library

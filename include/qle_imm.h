@@ -69,6 +69,11 @@ extern "C" {
 const char *qim_last_error(void);
 /* Diagnostics: kernel launches this library has made in this process so far (all threads). */
 int64_t qim_launch_count(void);
+/* Diagnostics: the launch census of this library, the contract of qle_launch_census_begin / _end (qle_ekf.h): the distinct
+ * kernels this library has launched since begin, process-wide; end stops the census and writes their mangled names, sorted,
+ * each followed by '\n', by the two-call size protocol.  Off, the census costs one relaxed atomic load per launch. */
+int qim_launch_census_begin(void);
+int qim_launch_census_end(char *names, int64_t cap, int64_t *needed);
 
 /* The mixing step of every bank of `view`, in place.  logmu = [batch] float64; Pi = [members][members] float64; mask = [batch]
  * bytes or NULL (all); logc = [batch] float64 (written); mixed = [batch] bytes or NULL (written).  ONE launch, writes view->state. */

@@ -55,6 +55,11 @@ extern "C" {
 const char *qsc_last_error(void);
 /* Diagnostics: kernel launches this library has made in this process so far (all threads). */
 int64_t qsc_launch_count(void);
+/* Diagnostics: the launch census of this library, the contract of qle_launch_census_begin / _end (qle_ekf.h): the distinct
+ * kernels this library has launched since begin, process-wide; end stops the census and writes their mangled names, sorted,
+ * each followed by '\n', by the two-call size protocol.  Off, the census costs one relaxed atomic load per launch. */
+int qsc_launch_census_begin(void);
+int qsc_launch_census_end(char *names, int64_t cap, int64_t *needed);
 
 /* Score the tag poses of one tick: `in` is the tick's inputs view and must have a tag slot (in->z) and IMU records,
  * already packed, and the tick must not have run yet (the innovation is taken against the state one prediction ahead

@@ -40,6 +40,11 @@ const char *qsq_last_error(void);
 /* Diagnostics: launches of k_sq_pack this library has made in this process so far (all threads).  The launches qsq_run
  * causes are counted by the libraries that make them (qgt_launch_count, qcs_launch_count, the tick library's census). */
 int64_t qsq_launch_count(void);
+/* Diagnostics: the launch census of this library, the contract of qle_launch_census_begin / _end (qle_ekf.h): the distinct
+ * kernels this library has launched since begin, process-wide; end stops the census and writes their mangled names, sorted,
+ * each followed by '\n', by the two-call size protocol.  Off, the census costs one relaxed atomic load per launch. */
+int qsq_launch_census_begin(void);
+int qsq_launch_census_end(char *names, int64_t cap, int64_t *needed);
 
 /* Fill ticks [t0, t0 + n) of `in`: u_seq = [n][batch][6]; z_seq = [m][batch][7] and mask_seq = [m][batch] (one byte per
  * filter, uint8 or bool; NULL = all set), m being the number of those ticks that have a tag slot, in tick order; all of

@@ -1,6 +1,6 @@
 """MI355X-native batched relative-pose EKF engine (drop-in for the hot path of
 mbrymer/quadrotor_landing's quad_state_estimation filter core)."""
-from ._lib import LIB_PATH, QLE_F32, QLE_F64, QleDerived, QleError, QleParams, QleSynthCfg, launch_census, lib  # noqa: F401
+from ._lib import LIB_PATH, QLE_F32, QLE_F64, QleDerived, QleError, QleParams, QleSynthCfg, launch_census, lib, side_launch_census  # noqa: F401
 from .ekf import BatchedRelativePoseEKF, InputSequence  # noqa: F401
 from .twin import RelativePoseEKF  # noqa: F401
 from .devio import DeviceIO  # noqa: F401

@@ -180,6 +180,9 @@ def check(rc):
     return rc
 
 
+SIDE_LIBRARIES = {}   # stem -> SideLibrary, every one the package has made
+
+
 class SideLibrary:
     """One of the libraries beside libqle_ekf.so (devio, gate, consistency, health, lookahead, sequence, score, bank, imm, adapt, stateio): where it is
     (`env` names the environment variable that overrides the in-tree path), what it exports (`symbols`, name -> (restype, argtypes)),
@@ -188,10 +191,12 @@ class SideLibrary:
     the handle uses (QLE_LIB included); `after`: side libraries it links, loaded before either."""
 
     def __init__(self, stem, env, symbols, what, last_error, needs_tick_library=False, after=()):
-        self.path = os.environ.get(env) or os.path.join(_HERE, f"libqle_{stem}.so")
+        self.stem, self.path = stem, os.environ.get(env) or os.path.join(_HERE, f"libqle_{stem}.so")
         self.symbols, self.what, self.last_error = symbols, what, last_error
+        self.prefix = last_error[:-len("_last_error")]
         self.needs_tick_library, self.after = needs_tick_library, tuple(after)
         self._handle = None
+        SIDE_LIBRARIES[stem] = self
 
     def load(self):
         """The bound library, loaded on the first call; raises (never falls back) when it is missing."""
@@ -209,6 +214,19 @@ class SideLibrary:
         if rc < 0:
             raise QleError(rc, getattr(self.load(), self.last_error)().decode())
         return rc
+
+    @contextlib.contextmanager
+    def launch_census(self):
+        """Diagnostics: the distinct kernels this library launches inside the block, process-wide (`<prefix>_launch_census_begin` /
+        `_end`).  Yields a list that is filled on exit with the kernels' demangled names, sorted by mangled name."""
+        L = self.load()
+        begin, end = getattr(L, self.prefix + "_launch_census_begin"), getattr(L, self.prefix + "_launch_census_end")
+        names = []
+        self.check(begin())
+        try:
+            yield names
+        finally:
+            names.extend(_census_names(end, self.check))
 
 
 _cxa = None
@@ -244,8 +262,27 @@ def launch_census():
     try:
         yield names
     finally:
-        need = _i64(0)
-        check(L.qle_launch_census_end(None, 0, C.byref(need)))
-        buf = C.create_string_buffer(need.value)
-        check(L.qle_launch_census_end(buf, need.value, C.byref(need)))
-        names.extend(demangle(n) for n in buf.value.decode().split("\n") if n)
+        names.extend(_census_names(L.qle_launch_census_end, check))
+
+
+def _census_names(end, check_rc):
+    """The list of a `*_launch_census_end` entry by its two-call size protocol, demangled."""
+    need = _i64(0)
+    check_rc(end(None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value)
+    check_rc(end(buf, need.value, C.byref(need)))
+    return [demangle(n) for n in buf.value.decode().split("\n") if n]
+
+
+@contextlib.contextmanager
+def side_launch_census():
+    """Diagnostics: `SideLibrary.launch_census` of every side library at once (each is loaded first).  Yields a dict that is filled on
+    exit: {library stem: [demangled kernel names]}, a library that launched nothing with an empty list."""
+    out = {}
+    with contextlib.ExitStack() as stack:
+        lists = {stem: stack.enter_context(side.launch_census()) for stem, side in sorted(SIDE_LIBRARIES.items())}
+        try:
+            yield out
+        finally:
+            stack.close()
+            out.update(lists)

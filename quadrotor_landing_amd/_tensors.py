@@ -21,6 +21,8 @@ SYMBOLS = {
     "qdv_unpack_report": (C.c_int, [_pview, _vp, _vp, _vp, _vp, C.c_int32]),
     "qdv_wait_stream": (C.c_int, [_pview, _vp]),
     "qdv_signal_stream": (C.c_int, [_pview, _vp]),
+    "qdv_launch_census_begin": (C.c_int, []),
+    "qdv_launch_census_end": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
 }
 DEVIO = SideLibrary("devio", "QLE_DEVIO_LIB", SYMBOLS, "the device-tensor boundary", "qdv_last_error")
 devio_lib, dcheck = DEVIO.load, DEVIO.check

@@ -39,6 +39,8 @@ _pd = C.POINTER(C.c_double)
 SYMBOLS = {
     "qad_last_error": (C.c_char_p, []),
     "qad_launch_count": (C.c_int64, []),
+    "qad_launch_census_begin": (C.c_int, []),
+    "qad_launch_census_end": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "qad_observe_tick": (C.c_int, [_pview, _pin, _ppar, _vp, C.c_double]),
     "qad_apply": (C.c_int, [_pview, _vp, _pcfg, _vp, _vp]),
     "qad_run": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _ppar, _vp, _pcfg]),

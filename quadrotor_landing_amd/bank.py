@@ -26,6 +26,8 @@ _pview = C.POINTER(QleDeviceView)
 SYMBOLS = {
     "qbk_last_error": (C.c_char_p, []),
     "qbk_launch_count": (C.c_int64, []),
+    "qbk_launch_census_begin": (C.c_int, []),
+    "qbk_launch_census_end": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "qbk_workspace_bytes": (C.c_int64, [_pview, C.c_int32]),
     "qbk_fuse": (C.c_int, [_pview, C.c_int32, _vp, _vp, _vp, C.c_int64, _pview, _vp, _vp]),
     "qbk_fuse_host": (C.c_int, [_pview, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint8), _vp, C.c_int64, _pview, C.POINTER(C.c_double),

@@ -27,6 +27,8 @@ _pd, _pu8 = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
 SYMBOLS = {
     "qcs_last_error": (C.c_char_p, []),
     "qcs_launch_count": (C.c_int64, []),
+    "qcs_launch_census_begin": (C.c_int, []),
+    "qcs_launch_census_end": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "qcs_nees": (C.c_int, [_pview, _ppar, _vp, C.c_int32, _vp, C.c_uint32, C.c_double, _vp, _vp, _vp, C.c_int32]),
     "qcs_nees_host": (C.c_int, [_pview, _ppar, _pd, _pu8, C.c_uint32, C.c_double, _pd, _pd, C.POINTER(QcsSummary)]),
 }

@@ -18,6 +18,7 @@ static_assert(QAD_WORDS == kAdaptWords, "the header publishes the accumulator re
 
 QLE_SIDE_LAST_ERROR(qad_last_error)
 QLE_SIDE_LAUNCH_COUNT(qad_launch_count)
+QLE_SIDE_LAUNCH_CENSUS(qad)
 
 static int check_params(const qle_params* p) { return check_observer_params(p, "noise adaptation"); }
 static int check_chi2(double chi2_max)
@@ -51,8 +52,8 @@ template <typename T>
 static int observe_t(const qle_device_view* v, const qle_inputs_view* in, const qle_params& pub, const qle_derived& der, double* acc, double chi2_max)
 {
     return launch_flags<T>(v, pub, der, [&](const DevParams<T>& dp, auto direct, auto, auto compact) {
-        hipLaunchKernelGGL((k_adapt_observe<T, decltype(direct)::value, decltype(compact)::value>), tiles(v), dim3(kTile), 0, stream_of(v), (const T*)v->state,
-                           (const T*)in->u, (const T*)in->z, v->batch, (const T*)v->filter_params, acc, v->padded_batch, chi2_max, dp);
+        return launch(k_adapt_observe<T, decltype(direct)::value, decltype(compact)::value>, tiles(v), dim3(kTile), 0, stream_of(v), (const T*)v->state,
+                      (const T*)in->u, (const T*)in->z, v->batch, (const T*)v->filter_params, acc, v->padded_batch, chi2_max, dp);
     });
 }
 static int observe_tick(const qle_device_view* v, const qle_inputs_view* in, const qle_params& pub, const qle_derived& der, double* acc, double chi2_max)
@@ -66,10 +67,8 @@ static int apply(const qle_device_view* v, double* acc, const qad_config& c, uin
     k.n_min = (double)c.n_min;
     for (int j = 0; j < 6; ++j) { k.lo[j] = c.R_lo[j]; k.hi[j] = c.R_hi[j]; }
     if (v->dtype == QLE_F32)
-        hipLaunchKernelGGL(k_adapt_apply<float>, tiles(v), dim3(kTile), 0, stream_of(v), (float*)v->filter_params, acc, v->batch, v->padded_batch, k, applied, R_out);
-    else
-        hipLaunchKernelGGL(k_adapt_apply<double>, tiles(v), dim3(kTile), 0, stream_of(v), (double*)v->filter_params, acc, v->batch, v->padded_batch, k, applied, R_out);
-    return launched();
+        return launch(k_adapt_apply<float>, tiles(v), dim3(kTile), 0, stream_of(v), (float*)v->filter_params, acc, v->batch, v->padded_batch, k, applied, R_out);
+    return launch(k_adapt_apply<double>, tiles(v), dim3(kTile), 0, stream_of(v), (double*)v->filter_params, acc, v->batch, v->padded_batch, k, applied, R_out);
 }
 
 extern "C" int qad_observe_tick(const qle_device_view* view, const qle_inputs_view* in, const qle_params* params, double* acc, double chi2_max)

@@ -13,6 +13,7 @@ static_assert(QBK_MAX_MEMBERS == kBankMaxMembers && kBankMaxMembers == kTile, "a
 
 QLE_SIDE_LAST_ERROR(qbk_last_error)
 QLE_SIDE_LAUNCH_COUNT(qbk_launch_count)
+QLE_SIDE_LAUNCH_CENSUS(qbk)
 
 static int64_t elt(const qle_device_view* v) { return v->dtype == QLE_F64 ? 8 : 4; }
 
@@ -62,11 +63,10 @@ static int launch_t(const qle_device_view* v, int32_t members, const double* log
 {
     const int64_t out_tiles = padded_filters(v->batch / members) / kTile;
     const dim3 grid((unsigned)(out_tiles * members));   // >= the input tiles; the workgroups past them fill the last output tile
-    with(v->compact != 0, [&](auto k) {
-        hipLaunchKernelGGL((k_bank_fuse<T, decltype(k)::value>), grid, dim3(kTile), 0, stream_of(v), (const T*)v->state, (T*)workspace, logw, mask, w, best,
-                           v->batch, members, (int32_t)(v->padded_batch / kTile));
+    return with(v->compact != 0, [&](auto k) {
+        return launch(k_bank_fuse<T, decltype(k)::value>, grid, dim3(kTile), 0, stream_of(v), (const T*)v->state, (T*)workspace, logw, mask, w, best,
+                      v->batch, members, (int32_t)(v->padded_batch / kTile));
     });
-    return launched();
 }
 
 static int run(const qle_device_view* v, int32_t members, const double* logw, const uint8_t* mask, void* workspace, qle_device_view* fused, double* w,

@@ -17,6 +17,7 @@ static_assert(sizeof(qcs_summary) == kNeesSums * sizeof(double), "k_nees_reduce 
 
 QLE_SIDE_LAST_ERROR(qcs_last_error)
 QLE_SIDE_LAUNCH_COUNT(qcs_launch_count)
+QLE_SIDE_LAUNCH_CENSUS(qcs)
 
 // Everything include/qle_consistency.h lists as refused; no GPU call.  The view may be larger than this library's (a smaller one is
 // refused).  host: the pointers are host arrays (no alignment to ask for, no dtypes).
@@ -56,15 +57,11 @@ static int launch_t(const qle_device_view* v, const qle_params& pub, const qle_d
     const dim3 grid((unsigned)tiles), block(kTile);
     hipStream_t s = (hipStream_t)v->stream;
     auto go = [&](auto pfp, auto compact) {
-        hipLaunchKernelGGL((k_nees<T, decltype(pfp)::value, decltype(compact)::value>), grid, block, 0, s, (const T*)v->state, c.x_true, v->batch,
-                           c.mask, (const T*)v->filter_params, c.nees, c.err, partials, c.blocks, v->num_states, c.true_f64, c.dst_f64, c.chi2_hi, dp);
+        return launch(k_nees<T, decltype(pfp)::value, decltype(compact)::value>, grid, block, 0, s, (const T*)v->state, c.x_true, v->batch,
+                      c.mask, (const T*)v->filter_params, c.nees, c.err, partials, c.blocks, v->num_states, c.true_f64, c.dst_f64, c.chi2_hi, dp);
     };
-    with(v->filter_params != nullptr, [&](auto f) { with(v->compact != 0, [&](auto k) { go(f, k); }); });
-    QLE_TRY(launched());
-    if (c.summary) {
-        hipLaunchKernelGGL(k_nees_reduce, dim3(1), dim3(kBlock), 0, s, (const double*)partials, tiles, c.summary);
-        QLE_TRY(launched());
-    }
+    QLE_TRY(with(v->filter_params != nullptr, [&](auto f) { return with(v->compact != 0, [&](auto k) { return go(f, k); }); }));
+    if (c.summary) QLE_TRY(launch(k_nees_reduce, dim3(1), dim3(kBlock), 0, s, (const double*)partials, tiles, c.summary));
     return QLE_OK;
 }
 

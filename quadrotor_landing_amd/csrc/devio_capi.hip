@@ -11,6 +11,7 @@ using namespace qdv;
 using namespace qle::side;
 
 QLE_SIDE_LAST_ERROR(qdv_last_error)
+QLE_SIDE_LAUNCH_CENSUS(qdv)
 
 // This library takes a view of exactly its own size and does not ask for aligned records (include/qle_devio.h).  No GPU call: every
 // entry refuses what it refuses first and calls use_device() behind that.
@@ -29,9 +30,7 @@ static int check_aligned(const void* p, const char* what)
 template <typename T, typename S>
 static int pack_t(const qle_device_view* v, const qle_inputs_view* in, const void* u, const void* z, const uint8_t* mask)
 {
-    k_dv_pack<T, S><<<tiles(v), dim3(kTile), 0, stream_of(v)>>>((const S*)u, (const S*)z, mask, (T*)in->u, (T*)in->z, v->batch);
-    HIP_TRY(hipGetLastError());
-    return QLE_OK;
+    return launch(k_dv_pack<T, S>, tiles(v), dim3(kTile), 0, stream_of(v), (const S*)u, (const S*)z, mask, (T*)in->u, (T*)in->z, v->batch);
 }
 
 extern "C" int qdv_pack_inputs(const qle_device_view* view, const qle_inputs_view* in, const void* u, const void* z, const uint8_t* mask, int32_t src_dtype)
@@ -51,10 +50,8 @@ extern "C" int qdv_pack_inputs(const qle_device_view* view, const qle_inputs_vie
 template <typename T, typename D>
 static int state_t(const qle_device_view* v, void* x, void* P)
 {
-    if (v->num_states == 15) k_dv_state<T, D, 15><<<tiles(v), dim3(kTile), 0, stream_of(v)>>>((const T*)v->state, (D*)x, (D*)P, v->batch, 0);
-    else k_dv_state<T, D, 9><<<tiles(v), dim3(kTile), 0, stream_of(v)>>>((const T*)v->state, (D*)x, (D*)P, v->batch, (int)v->compact);
-    HIP_TRY(hipGetLastError());
-    return QLE_OK;
+    if (v->num_states == 15) return launch(k_dv_state<T, D, 15>, tiles(v), dim3(kTile), 0, stream_of(v), (const T*)v->state, (D*)x, (D*)P, v->batch, 0);
+    return launch(k_dv_state<T, D, 9>, tiles(v), dim3(kTile), 0, stream_of(v), (const T*)v->state, (D*)x, (D*)P, v->batch, (int)v->compact);
 }
 
 extern "C" int qdv_unpack_state(const qle_device_view* view, void* x, void* P, int32_t dst_dtype)
@@ -74,10 +71,8 @@ static int report_t(const qle_device_view* v, void* pose, void* cov, void* vel, 
 {
     StaticBias sb;
     for (int k = 0; k < 3; ++k) { sb.v[k] = v->ab_static[k]; sb.v[3 + k] = v->wb_static[k]; }
-    k_dv_report<T, D><<<tiles(v), dim3(kTile), 0, stream_of(v)>>>((const T*)v->state, (const T*)v->filter_params, (D*)pose, (D*)cov, (D*)vel, (D*)bias,
-                                                                 v->batch, (int)v->compact, sb);
-    HIP_TRY(hipGetLastError());
-    return QLE_OK;
+    return launch(k_dv_report<T, D>, tiles(v), dim3(kTile), 0, stream_of(v), (const T*)v->state, (const T*)v->filter_params, (D*)pose, (D*)cov, (D*)vel, (D*)bias,
+                  v->batch, (int)v->compact, sb);
 }
 
 extern "C" int qdv_unpack_report(const qle_device_view* view, void* pose, void* pose_cov, void* vel, void* bias, int32_t dst_dtype)

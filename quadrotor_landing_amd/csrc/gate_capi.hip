@@ -13,6 +13,7 @@ using namespace qle::side;
 
 QLE_SIDE_LAST_ERROR(qgt_last_error)
 QLE_SIDE_LAUNCH_COUNT(qgt_launch_count)
+QLE_SIDE_LAUNCH_CENSUS(qgt)
 
 // Everything include/qle_gate.h lists as refused; no GPU call.  multirate_ekf is QLE_ERR_STATE, another class of error than the rest,
 // and stays ahead of what is refused about the view's fields; the view may be larger than this library's (a smaller one is refused).
@@ -37,8 +38,8 @@ template <typename T, bool PREDICT>
 static int launch_t(const qle_device_view* v, const qle_inputs_view* in, const qle_params& pub, const qle_derived& der, const Outs& o)
 {
     return launch_flags<T>(v, pub, der, [&](const DevParams<T>& dp, auto direct, auto pfp, auto compact) {
-        hipLaunchKernelGGL((k_pregate<T, decltype(direct)::value, decltype(pfp)::value, decltype(compact)::value, PREDICT>), tiles(v), dim3(kTile), 0, stream_of(v),
-                           (const T*)v->state, (const T*)in->u, (T*)in->z, v->batch, (const T*)v->filter_params, o.nis, o.accepted, o.nu, o.S, o.f64, o.chi2_max, dp);
+        return launch(k_pregate<T, decltype(direct)::value, decltype(pfp)::value, decltype(compact)::value, PREDICT>, tiles(v), dim3(kTile), 0, stream_of(v),
+                      (const T*)v->state, (const T*)in->u, (T*)in->z, v->batch, (const T*)v->filter_params, o.nis, o.accepted, o.nu, o.S, o.f64, o.chi2_max, dp);
     });
 }
 

@@ -17,6 +17,7 @@ static_assert(QHL_ALL == kHealthAllBits && QHL_NONFINITE == kHealthNonfinite && 
 
 QLE_SIDE_LAST_ERROR(qhl_last_error)
 QLE_SIDE_LAUNCH_COUNT(qhl_launch_count)
+QLE_SIDE_LAUNCH_CENSUS(qhl)
 
 // what every entry refuses about the view; no GPU call.  The view may be larger than this library's (a smaller one is refused); the
 // kernels read the records in 16-byte rows, so the records have to be aligned.
@@ -44,17 +45,13 @@ static int health_t(const qle_device_view* v, const HealthLimits& lim, const uin
     const dim3 grid((unsigned)tiles), block(kTile);
     hipStream_t s = (hipStream_t)v->stream;
     auto go = [&](auto compact, auto n) {
-        hipLaunchKernelGGL((k_health<T, decltype(compact)::value, decltype(n)::value>), grid, block, 0, s, (const T*)v->state, v->batch, mask, status, flagged,
-                           partials, lim);
+        return launch(k_health<T, decltype(compact)::value, decltype(n)::value>, grid, block, 0, s, (const T*)v->state, v->batch, mask, status, flagged,
+                      partials, lim);
     };
-    if (v->compact) go(std::true_type{}, std::integral_constant<int, 9>{});
-    else if (v->num_states == 9) go(std::false_type{}, std::integral_constant<int, 9>{});
-    else go(std::false_type{}, std::integral_constant<int, 15>{});
-    QLE_TRY(launched());
-    if (summary) {
-        hipLaunchKernelGGL(k_health_reduce, dim3(1), dim3(kBlock), 0, s, (const double*)partials, tiles, summary);
-        QLE_TRY(launched());
-    }
+    if (v->compact) QLE_TRY(go(std::true_type{}, std::integral_constant<int, 9>{}));
+    else if (v->num_states == 9) QLE_TRY(go(std::false_type{}, std::integral_constant<int, 9>{}));
+    else QLE_TRY(go(std::false_type{}, std::integral_constant<int, 15>{}));
+    if (summary) QLE_TRY(launch(k_health_reduce, dim3(1), dim3(kBlock), 0, s, (const double*)partials, tiles, summary));
     return QLE_OK;
 }
 
@@ -83,9 +80,8 @@ extern "C" int qhl_retire(const qle_device_view* view, const uint8_t* mask)
     QLE_TRY(use_device(view));
     const dim3 grid((unsigned)(view->padded_batch / kTile)), block(kTile);
     hipStream_t s = (hipStream_t)view->stream;
-    if (view->dtype == QLE_F32) hipLaunchKernelGGL(k_retire<float>, grid, block, 0, s, (float*)view->state, mask, view->batch, view->compact);
-    else hipLaunchKernelGGL(k_retire<double>, grid, block, 0, s, (double*)view->state, mask, view->batch, view->compact);
-    return launched();
+    if (view->dtype == QLE_F32) return launch(k_retire<float>, grid, block, 0, s, (float*)view->state, mask, view->batch, view->compact);
+    return launch(k_retire<double>, grid, block, 0, s, (double*)view->state, mask, view->batch, view->compact);
 }
 
 extern "C" int qhl_and_masks(const qle_device_view* view, const uint8_t* a, const uint8_t* b, uint8_t* out)
@@ -93,8 +89,7 @@ extern "C" int qhl_and_masks(const qle_device_view* view, const uint8_t* a, cons
     QLE_TRY(check_view(view));
     if (!a || !b || !out) return fail(QLE_ERR_INVALID, "a, b and out must not be null");
     QLE_TRY(use_device(view));
-    hipLaunchKernelGGL(k_and_masks, dim3((unsigned)((view->batch + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)view->stream, a, b, out, view->batch);
-    return launched();
+    return launch(k_and_masks, dim3((unsigned)((view->batch + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)view->stream, a, b, out, view->batch);
 }
 
 extern "C" int qhl_health_host(const qle_device_view* view, const qhl_limits* limits, const uint8_t* mask, uint8_t* status, uint8_t* flagged,

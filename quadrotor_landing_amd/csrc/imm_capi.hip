@@ -13,6 +13,7 @@ static_assert(kBankMaxMembers == kTile, "a bank never leaves one wave tile");
 
 QLE_SIDE_LAST_ERROR(qim_last_error)
 QLE_SIDE_LAUNCH_COUNT(qim_launch_count)
+QLE_SIDE_LAUNCH_CENSUS(qim)
 
 // what every entry refuses about the view and the geometry (the rules of bank_capi.hip); no GPU call
 static int check_geometry(const qle_device_view* v, int32_t members)
@@ -47,10 +48,9 @@ static int check_mix(const qle_device_view* v, const qle_params* p, int32_t memb
 template <typename T>
 static int launch_mix(const qle_device_view* v, int32_t members, const double* logmu, const double* Pi, const uint8_t* mask, double* logc, uint8_t* mixed)
 {
-    with(v->compact != 0, [&](auto k) {
-        hipLaunchKernelGGL((k_imm_mix<T, decltype(k)::value>), tiles(v), dim3(kTile), 0, stream_of(v), (T*)v->state, logmu, Pi, mask, logc, mixed, v->batch, members);
+    return with(v->compact != 0, [&](auto k) {
+        return launch(k_imm_mix<T, decltype(k)::value>, tiles(v), dim3(kTile), 0, stream_of(v), (T*)v->state, logmu, Pi, mask, logc, mixed, v->batch, members);
     });
-    return launched();
 }
 
 // behind every refusal and use_device
@@ -77,8 +77,7 @@ extern "C" int qim_update(const qle_device_view* view, int32_t members, const do
     if (!aligned(logc, 8) || !aligned(loglik, 8) || !aligned(logmu, 8)) return fail(QLE_ERR_INVALID, "logc, loglik and logmu must be 8-byte aligned");
     if (logmu_min != logmu_min) return fail(QLE_ERR_INVALID, "logmu_min is NaN");
     QLE_TRY(use_device(view));
-    hipLaunchKernelGGL(k_imm_update, tiles(view), dim3(kTile), 0, stream_of(view), logc, loglik, mask, logmu_min, logmu, view->batch, members);
-    return launched();
+    return launch(k_imm_update, tiles(view), dim3(kTile), 0, stream_of(view), logc, loglik, mask, logmu_min, logmu, view->batch, members);
 }
 
 extern "C" int qim_mix_host(const qle_device_view* view, const qle_params* params, int32_t members, const double* logmu, const double* Pi, const uint8_t* mask,

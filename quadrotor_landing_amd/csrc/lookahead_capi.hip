@@ -17,6 +17,7 @@ static_assert(QLK_MAX_HORIZON == kMaxHorizon, "the horizon cap of the header");
 
 QLE_SIDE_LAST_ERROR(qlk_last_error)
 QLE_SIDE_LAUNCH_COUNT(qlk_launch_count)
+QLE_SIDE_LAUNCH_CENSUS(qlk)
 
 // what every entry refuses about the view; no GPU call.  A view of exactly this library's size (the forecast is a copy of it), with
 // 16-byte aligned records.
@@ -72,11 +73,10 @@ static int launch_t(const qle_device_view* v, const qle_params& pub, const qle_d
     DevParams<T> dp = make_dev<T>(pub, der);
     dp.compact = v->compact ? 1 : 0;
     auto go = [&](auto pfp, auto compact) {
-        hipLaunchKernelGGL((k_lookahead<T, decltype(pfp)::value, decltype(compact)::value>), tiles(v), dim3(kTile), 0, stream_of(v), (const T*)v->state, (T*)c.workspace, c.u,
-                           v->batch, c.h, c.u_f64, c.mask, (const T*)v->filter_params, c.ticks, c.lim, dp);
+        return launch(k_lookahead<T, decltype(pfp)::value, decltype(compact)::value>, tiles(v), dim3(kTile), 0, stream_of(v), (const T*)v->state, (T*)c.workspace, c.u,
+                      v->batch, c.h, c.u_f64, c.mask, (const T*)v->filter_params, c.ticks, c.lim, dp);
     };
-    with(v->filter_params != nullptr, [&](auto f) { with(v->compact != 0, [&](auto k) { go(f, k); }); });
-    return launched();
+    return with(v->filter_params != nullptr, [&](auto f) { return with(v->compact != 0, [&](auto k) { return go(f, k); }); });
 }
 
 // the launch and the forecast view; the arguments are checked

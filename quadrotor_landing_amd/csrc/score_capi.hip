@@ -14,6 +14,7 @@ static_assert(QSC_WORDS == kScoreWords && QSC_SUMS == kScoreSums, "the header pu
 
 QLE_SIDE_LAST_ERROR(qsc_last_error)
 QLE_SIDE_LAUNCH_COUNT(qsc_launch_count)
+QLE_SIDE_LAUNCH_CENSUS(qsc)
 
 static int check_params(const qle_params* p) { return check_observer_params(p, "scoring"); }
 
@@ -22,8 +23,8 @@ template <typename T>
 static int launch_t(const qle_device_view* v, const qle_inputs_view* in, const qle_params& pub, const qle_derived& der, double* acc)
 {
     return launch_flags<T>(v, pub, der, [&](const DevParams<T>& dp, auto direct, auto pfp, auto compact) {
-        hipLaunchKernelGGL((k_score<T, decltype(direct)::value, decltype(pfp)::value, decltype(compact)::value>), tiles(v), dim3(kTile), 0, stream_of(v), (const T*)v->state,
-                           (const T*)in->u, (const T*)in->z, v->batch, (const T*)v->filter_params, acc, v->padded_batch, dp);
+        return launch(k_score<T, decltype(direct)::value, decltype(pfp)::value, decltype(compact)::value>, tiles(v), dim3(kTile), 0, stream_of(v), (const T*)v->state,
+                      (const T*)in->u, (const T*)in->z, v->batch, (const T*)v->filter_params, acc, v->padded_batch, dp);
     });
 }
 static int score_tick(const qle_device_view* v, const qle_inputs_view* in, const qle_params& pub, const qle_derived& der, double* acc)
@@ -87,8 +88,6 @@ extern "C" int qsc_summary(const qle_device_view* view, const double* acc, const
     const int64_t nt = view->padded_batch / kTile;
     double* partials = nullptr;
     QLE_TRY(g_partials.get(view, nt, &partials));
-    hipLaunchKernelGGL(k_score_tiles, tiles(view), dim3(kTile), 0, stream_of(view), acc, view->batch, view->padded_batch, mask, partials);
-    QLE_TRY(launched());
-    hipLaunchKernelGGL(k_score_reduce, dim3(1), dim3(kBlock), 0, stream_of(view), (const double*)partials, nt, out30);
-    return launched();
+    QLE_TRY(launch(k_score_tiles, tiles(view), dim3(kTile), 0, stream_of(view), acc, view->batch, view->padded_batch, mask, partials));
+    return launch(k_score_reduce, dim3(1), dim3(kBlock), 0, stream_of(view), (const double*)partials, nt, out30);
 }

@@ -18,6 +18,7 @@ static_assert(sizeof(qcs_summary) == 8 * sizeof(double), "summary slices are eig
 
 QLE_SIDE_LAST_ERROR(qsq_last_error)
 QLE_SIDE_LAUNCH_COUNT(qsq_launch_count)
+QLE_SIDE_LAUNCH_CENSUS(qsq)
 
 static int check_dtype(int32_t d, const char* what)
 {
@@ -59,9 +60,8 @@ static int pack_t(const qle_device_view* v, const std::vector<PlanChunk>& plan, 
             chunk.e[y].z = (T*)iv.z;
             chunk.e[y].zsrc = c.e[y].zsrc;
         }
-        k_sq_pack<T, S><<<dim3((unsigned)(v->padded_batch / kTile), (unsigned)c.count), dim3(kTile), 0, stream_of(v)>>>((const S*)u_seq, (const S*)z_seq, mask_seq,
-                                                                                                                     v->batch, c.k0, chunk);
-        QLE_TRY(launched());
+        QLE_TRY(launch(k_sq_pack<T, S>, dim3((unsigned)(v->padded_batch / kTile), (unsigned)c.count), dim3(kTile), 0, stream_of(v), (const S*)u_seq, (const S*)z_seq,
+                       mask_seq, v->batch, c.k0, chunk));
     }
     return QLE_OK;
 }

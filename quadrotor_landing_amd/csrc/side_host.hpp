@@ -1,20 +1,24 @@
 // side_host.hpp -- the host scaffold the side libraries share (devio, gate, consistency, health, lookahead, sequence, score, bank, imm, adapt, stateio: csrc/Makefile, SIDE).
-// Host code only, every symbol internal: a library that includes it has an error string and a launch counter of its own, and
-// exports nothing it did not export before.  A *_capi.hip file keeps its static_asserts, the refusals that are its own, its launches
+// Host code only, every symbol internal: a library that includes it has an error string, a launch counter and a launch census of its
+// own, and exports what its QLE_SIDE_* lines name.  A *_capi.hip file keeps its static_asserts, the refusals that are its own, its launches
 // and its extern "C" entries; what every one of them needs around those is here.
 #pragma once
 
+#include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 #include "../../include/qle_ekf.h"
 #include "device_mem.hpp"
@@ -49,6 +53,68 @@ int launched()
     return QLE_OK;
 }
 
+// ---- launch census: the distinct kernels launch() has launched since <prefix>_launch_census_begin, process-wide and per library (the
+// contract of qle_launch_census_begin / _end, include/qle_ekf.h).  A process may drive handles from several host threads, so the list
+// is guarded by a mutex; while the census is off, launch() pays one relaxed atomic load.
+std::atomic<bool> g_census_on{false};
+std::mutex g_census_mu;
+std::vector<const void*> g_census;
+
+void census_record(const void* kernel)
+{
+    std::lock_guard<std::mutex> lock(g_census_mu);
+    if (g_census_on.load(std::memory_order_relaxed) && std::find(g_census.begin(), g_census.end(), kernel) == g_census.end()) g_census.push_back(kernel);
+}
+int census_begin()
+{
+    std::lock_guard<std::mutex> lock(g_census_mu);
+    g_census.clear();
+    g_census_on.store(true, std::memory_order_relaxed);
+    return QLE_OK;
+}
+// The host handle of a kernel is an exported symbol of the library whose name is the device kernel's mangled name; a handle the
+// dynamic symbol table does not name is asked of the runtime.
+const char* kernel_name(const void* kernel)
+{
+    Dl_info info;
+    if (dladdr(kernel, &info) && info.dli_sname && info.dli_saddr == kernel) return info.dli_sname;
+    return hipKernelNameRefByPtr(kernel, nullptr);
+}
+// stops the census; the list stays until the next begin, so it may be called again with a larger buffer
+int census_end(char* names, int64_t cap, int64_t* needed)
+{
+    std::lock_guard<std::mutex> lock(g_census_mu);
+    g_census_on.store(false, std::memory_order_relaxed);
+    std::vector<std::string> list;
+    for (const void* k : g_census) {
+        const char* n = kernel_name(k);
+        if (!n) return fail(QLE_ERR_INVALID, "launch census: no symbol name for the kernel at %p", k);
+        list.emplace_back(n);
+    }
+    std::sort(list.begin(), list.end());
+    std::string out;
+    for (const std::string& n : list) out += n + "\n";
+    if (needed) *needed = (int64_t)out.size() + 1;
+    if (names) {
+        if (cap < (int64_t)out.size() + 1) return fail(QLE_ERR_INVALID, "launch census: %lld bytes needed, %lld given", (long long)out.size() + 1, (long long)cap);
+        std::memcpy(names, out.c_str(), out.size() + 1);
+    }
+    return QLE_OK;
+}
+// the two census entries of a library's header: <prefix>_launch_census_begin and <prefix>_launch_census_end
+#define QLE_SIDE_LAUNCH_CENSUS(prefix)                                                                                        \
+    extern "C" int prefix##_launch_census_begin(void) { return qle::side::census_begin(); }                                   \
+    extern "C" int prefix##_launch_census_end(char* names, int64_t cap, int64_t* needed) { return qle::side::census_end(names, cap, needed); }
+
+// Every kernel launch of a side library: the census sees the kernel's host handle, the runtime takes the launch, launched() counts it.
+template <typename... P, typename... Args>
+int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args)
+{
+    if (g_census_on.load(std::memory_order_relaxed)) census_record(reinterpret_cast<const void*>(kernel));
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    return launched();
+}
+
 bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // view->struct_size: the libraries differ, on purpose, and say which rule they keep where they call check_view
@@ -80,12 +146,12 @@ int use_device(const qle_device_view* v)
 inline dim3 tiles(const qle_device_view* v) { return dim3((unsigned)(v->padded_batch / kTile)); }
 inline hipStream_t stream_of(const qle_device_view* v) { return (hipStream_t)v->stream; }
 
-// a run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{})
+// a run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{}), and what it returns
 template <typename F>
-void with(bool b, F&& f)
+auto with(bool b, F&& f)
 {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
+    if (b) return f(std::true_type{});
+    return f(std::false_type{});
 }
 
 // The [tiles][sums] partials of a batch summary: one buffer per (device, stream), grown on demand and kept -- two calls on one

@@ -18,14 +18,16 @@ int derive(const qle_params* p, qle_derived* der)
     return qle_params_derive(p, der) == QLE_OK ? QLE_OK : fail(QLE_ERR_INVALID, "params: %s", qle_last_error());
 }
 // One launch on the view's records: go(dp, direct, pfp, compact) with the device parameter block and the three flags of the view and the
-// parameters as std::true_type / std::false_type; go launches.  Behind every refusal and use_device.
+// parameters as std::true_type / std::false_type; go launches through launch() (side_host.hpp) and returns its status.  Behind every
+// refusal and use_device.
 template <typename T, typename Go>
 int launch_flags(const qle_device_view* v, const qle_params& pub, const qle_derived& der, Go&& go)
 {
     DevParams<T> dp = make_dev<T>(pub, der);
     dp.compact = v->compact ? 1 : 0;
-    with(pub.direct_orien_method != 0, [&](auto d) { with(v->filter_params != nullptr, [&](auto f) { with(v->compact != 0, [&](auto c) { go(dp, d, f, c); }); }); });
-    return launched();
+    return with(pub.direct_orien_method != 0, [&](auto d) {
+        return with(v->filter_params != nullptr, [&](auto f) { return with(v->compact != 0, [&](auto c) { return go(dp, d, f, c); }); });
+    });
 }
 
 int inputs_view(const qle_inputs* in, int64_t t, qle_inputs_view* iv)

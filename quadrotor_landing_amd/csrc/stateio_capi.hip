@@ -15,6 +15,7 @@ static_assert(qsi::quads_of(kXW + kPW, 4) == qsi::kCopyBatch && qsi::quads_of(kX
 
 QLE_SIDE_LAST_ERROR(qsi_last_error)
 QLE_SIDE_LAUNCH_COUNT(qsi_launch_count)
+QLE_SIDE_LAUNCH_CENSUS(qsi)
 
 static int wsz(const qle_device_view* v) { return v->dtype == QLE_F64 ? 8 : 4; }
 static int64_t state_bytes(const qle_device_view* v) { return v->padded_batch * (int64_t)kSW * wsz(v); }
@@ -43,15 +44,15 @@ extern "C" int64_t qsi_workspace_bytes(const qle_device_view* view)
 
 // ------------------------------------------------------------------ pack
 template <typename T, typename S>
-static void launch_pack(const qle_device_view* v, const void* x, const void* P, const uint8_t* mask)
+static int launch_pack(const qle_device_view* v, const void* x, const void* P, const uint8_t* mask)
 {
     auto go = [&](auto n, auto compact) {
-        hipLaunchKernelGGL((qsi::k_si_pack<T, S, decltype(n)::value, decltype(compact)::value>), tiles(v), dim3(kTile), 0, stream_of(v), (const S*)x, (const S*)P,
-                           mask, (T*)v->state, v->batch);
+        return launch(qsi::k_si_pack<T, S, decltype(n)::value, decltype(compact)::value>, tiles(v), dim3(kTile), 0, stream_of(v), (const S*)x, (const S*)P,
+                      mask, (T*)v->state, v->batch);
     };
-    if (v->compact) go(std::integral_constant<int, 9>{}, std::true_type{});
-    else if (v->num_states == 9) go(std::integral_constant<int, 9>{}, std::false_type{});
-    else go(std::integral_constant<int, 15>{}, std::false_type{});
+    if (v->compact) return go(std::integral_constant<int, 9>{}, std::true_type{});
+    if (v->num_states == 9) return go(std::integral_constant<int, 9>{}, std::false_type{});
+    return go(std::integral_constant<int, 15>{}, std::false_type{});
 }
 
 extern "C" int qsi_pack_state(const qle_device_view* view, const void* x, const void* P, int32_t src_dtype, const uint8_t* mask)
@@ -63,9 +64,8 @@ extern "C" int qsi_pack_state(const qle_device_view* view, const void* x, const 
     if (!aligned(P, 16)) return fail(QLE_ERR_INVALID, "P must be 16-byte aligned");
     QLE_TRY(use_device(view));
     const bool s64 = src_dtype == QSI_F64;
-    if (view->dtype == QLE_F32) s64 ? launch_pack<float, double>(view, x, P, mask) : launch_pack<float, float>(view, x, P, mask);
-    else s64 ? launch_pack<double, double>(view, x, P, mask) : launch_pack<double, float>(view, x, P, mask);
-    return launched();
+    if (view->dtype == QLE_F32) return s64 ? launch_pack<float, double>(view, x, P, mask) : launch_pack<float, float>(view, x, P, mask);
+    return s64 ? launch_pack<double, double>(view, x, P, mask) : launch_pack<double, float>(view, x, P, mask);
 }
 
 // ------------------------------------------------------------------ copy
@@ -97,21 +97,20 @@ static int check_copy(const qle_device_view* s, const qle_device_view* d, const 
 static int run_copy(const qle_device_view* s, const qle_device_view* d, const int32_t* index, const uint8_t* mask, int32_t with_params, uint8_t* written)
 {
     auto go = [&](auto rows, auto recq, auto parq) {
-        hipLaunchKernelGGL((qsi::k_si_copy<decltype(rows)::value, decltype(recq)::value, decltype(parq)::value>), tiles(d), dim3(kTile), 0, stream_of(d),
-                           (const qsi::qsi_u4*)s->state, (qsi::qsi_u4*)d->state, index, mask, s->batch, d->batch,
-                           (const qsi::qsi_u4*)(with_params ? s->filter_params : nullptr), (qsi::qsi_u4*)(with_params ? d->filter_params : nullptr), written);
+        return launch(qsi::k_si_copy<decltype(rows)::value, decltype(recq)::value, decltype(parq)::value>, tiles(d), dim3(kTile), 0, stream_of(d),
+                      (const qsi::qsi_u4*)s->state, (qsi::qsi_u4*)d->state, index, mask, s->batch, d->batch,
+                      (const qsi::qsi_u4*)(with_params ? s->filter_params : nullptr), (qsi::qsi_u4*)(with_params ? d->filter_params : nullptr), written);
     };
     using std::integral_constant;
     auto by_dtype = [&](auto w) {
         constexpr int W = decltype(w)::value;
         constexpr integral_constant<int, qsi::quads_of(kSW, W)> recq{};
         constexpr integral_constant<int, qsi::quads_of(kFW, W)> parq{};
-        if (d->compact) go(integral_constant<int, qsi::quads_of(kXW + kPWc, W)>{}, recq, parq);
-        else go(integral_constant<int, qsi::quads_of(kXW + kPW, W)>{}, recq, parq);
+        if (d->compact) return go(integral_constant<int, qsi::quads_of(kXW + kPWc, W)>{}, recq, parq);
+        return go(integral_constant<int, qsi::quads_of(kXW + kPW, W)>{}, recq, parq);
     };
-    if (d->dtype == QLE_F32) by_dtype(integral_constant<int, 4>{});
-    else by_dtype(integral_constant<int, 8>{});
-    return launched();
+    if (d->dtype == QLE_F32) return by_dtype(integral_constant<int, 4>{});
+    return by_dtype(integral_constant<int, 8>{});
 }
 
 extern "C" int qsi_copy(const qle_device_view* src, const qle_device_view* dst, const int32_t* index, const uint8_t* mask, int32_t with_params,

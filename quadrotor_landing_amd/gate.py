@@ -18,6 +18,8 @@ SYMBOLS = {
     "qgt_gate_tick": (C.c_int, [_pview, _pin, _ppar, C.c_double, _vp, _vp, _vp, _vp, C.c_int32]),
     "qgt_innovation": (C.c_int, [_pview, _pin, _ppar, _vp, _vp, _vp, C.c_int32]),
     "qgt_launch_count": (C.c_int64, []),
+    "qgt_launch_census_begin": (C.c_int, []),
+    "qgt_launch_census_end": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
 }
 
 GATE = SideLibrary("gate", "QLE_GATE_LIB", SYMBOLS, "the gate in front of the fused tick", "qgt_last_error", needs_tick_library=True)

@@ -35,6 +35,8 @@ _pu8 = C.POINTER(C.c_uint8)
 SYMBOLS = {
     "qhl_last_error": (C.c_char_p, []),
     "qhl_launch_count": (C.c_int64, []),
+    "qhl_launch_census_begin": (C.c_int, []),
+    "qhl_launch_census_end": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "qhl_health": (C.c_int, [_pview, _plim, _vp, _vp, _vp, _vp]),
     "qhl_health_host": (C.c_int, [_pview, _plim, _pu8, _pu8, _pu8, C.POINTER(QhlSummary)]),
     "qhl_retire": (C.c_int, [_pview, _vp]),

@@ -28,6 +28,8 @@ _pd, _pu8 = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
 SYMBOLS = {
     "qim_last_error": (C.c_char_p, []),
     "qim_launch_count": (C.c_int64, []),
+    "qim_launch_census_begin": (C.c_int, []),
+    "qim_launch_census_end": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "qim_mix": (C.c_int, [_pview, _ppar, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "qim_update": (C.c_int, [_pview, C.c_int32, _vp, _vp, _vp, C.c_double, _vp]),
     "qim_mix_host": (C.c_int, [_pview, _ppar, C.c_int32, _pd, _pd, _pu8, _pd, _pu8]),

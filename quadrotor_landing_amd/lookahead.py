@@ -28,6 +28,8 @@ _pview, _pparams, _pcoast = C.POINTER(QleDeviceView), C.POINTER(QleParams), C.PO
 SYMBOLS = {
     "qlk_last_error": (C.c_char_p, []),
     "qlk_launch_count": (C.c_int64, []),
+    "qlk_launch_census_begin": (C.c_int, []),
+    "qlk_launch_census_end": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "qlk_workspace_bytes": (C.c_int64, [_pview]),
     "qlk_lookahead": (C.c_int, [_pview, _pparams, _vp, C.c_int32, C.c_int32, _vp, _vp, C.c_int64, _pview, _pcoast, _vp]),
     "qlk_lookahead_host": (C.c_int, [_pview, _pparams, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_uint8), _vp, C.c_int64, _pview, _pcoast,

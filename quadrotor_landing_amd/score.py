@@ -26,6 +26,8 @@ _pview, _pin, _ppar = C.POINTER(QleDeviceView), C.POINTER(QleInputsView), C.POIN
 SYMBOLS = {
     "qsc_last_error": (C.c_char_p, []),
     "qsc_launch_count": (C.c_int64, []),
+    "qsc_launch_census_begin": (C.c_int, []),
+    "qsc_launch_census_end": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "qsc_score_tick": (C.c_int, [_pview, _pin, _ppar, _vp]),
     "qsc_run": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _ppar, _vp]),
     "qsc_summary": (C.c_int, [_pview, _vp, _vp, _vp]),

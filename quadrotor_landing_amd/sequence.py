@@ -33,6 +33,8 @@ class QsqRunOpts(C.Structure):
 SYMBOLS = {
     "qsq_last_error": (C.c_char_p, []),
     "qsq_launch_count": (C.c_int64, []),
+    "qsq_launch_census_begin": (C.c_int, []),
+    "qsq_launch_census_end": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "qsq_pack": (C.c_int, [C.POINTER(QleDeviceView), _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32]),
     "qsq_run": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(QsqRunOpts)]),
 }

@@ -27,6 +27,8 @@ _pview = C.POINTER(QleDeviceView)
 SYMBOLS = {
     "qsi_last_error": (C.c_char_p, []),
     "qsi_launch_count": (C.c_int64, []),
+    "qsi_launch_census_begin": (C.c_int, []),
+    "qsi_launch_census_end": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "qsi_workspace_bytes": (C.c_int64, [_pview]),
     "qsi_pack_state": (C.c_int, [_pview, _vp, _vp, C.c_int32, _vp]),
     "qsi_copy": (C.c_int, [_pview, _pview, _vp, _vp, C.c_int32, _vp]),

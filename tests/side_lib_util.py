@@ -1,4 +1,4 @@
-"""What the CPU tests of the side libraries (devio, gate, consistency, health, lookahead, sequence, score, bank, imm) share: building a
+"""What the CPU tests of the side libraries (devio, gate, consistency, health, lookahead, sequence, score, bank, imm, adapt, stateio) share: building a
 library that is missing, holding its exports to its header and its binding, the stale-EXEC audit and the kernel descriptors of the
 generated assembly, and the stand-ins that let an entry point or DeviceIO be called without a GPU.  What a library expects -- its
 names, kernel counts, families, bounds -- stays in its own test."""

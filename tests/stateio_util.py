@@ -6,8 +6,9 @@ import numpy as np
 SW, XW, PW, PWC = 144, 16, 120, 48
 RECORD_WORDS = {False: 136, True: 64}
 NP_T = {"f32": np.float32, "f64": np.float64}
-# the four record kinds: name -> (dtype, num_states, compact)
-KINDS = {"f32-full": ("f32", 15, False), "f32-compact": ("f32", 9, True), "f64-full": ("f64", 15, False), "f64-compact": ("f64", 9, True)}
+# the six record kinds: name -> (dtype, num_states, compact); full9 is what an est_bias = 0 handle holds unless compact records are chosen
+KINDS = {"f32-full": ("f32", 15, False), "f32-full9": ("f32", 9, False), "f32-compact": ("f32", 9, True),
+         "f64-full": ("f64", 15, False), "f64-full9": ("f64", 9, False), "f64-compact": ("f64", 9, True)}
 
 
 def padded(B):

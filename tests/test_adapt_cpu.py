@@ -43,7 +43,7 @@ def adapt_so():
 
 def test_library_exports_and_binds_every_declared_function(adapt_so):
     _, txt = assert_exports_and_binds(adapt, HEADER, "qad", adapt_so,
-                                      ["qad_apply", "qad_last_error", "qad_launch_count", "qad_observe_tick", "qad_run", "qad_run_host"])
+                                      ["qad_apply", "qad_last_error", "qad_launch_census_begin", "qad_launch_census_end", "qad_launch_count", "qad_observe_tick", "qad_run", "qad_run_host"])
     assert adapt.WORDS == int(re.search(r"#define QAD_WORDS (\d+)", txt).group(1)) == 24
     assert C.sizeof(adapt.QadConfig) == 4 + 4 + 8 + 4 + 4 + 8 + 48 + 48
 

@@ -40,7 +40,7 @@ def bank_so():
 # ---------------------------------------------------------------- 1. header, exports, kernels, audit, resources
 def test_library_exports_and_binds_every_declared_function(bank_so):
     _, txt = assert_exports_and_binds(bank, HEADER, "qbk", bank_so,
-                                      ["qbk_fuse", "qbk_fuse_host", "qbk_last_error", "qbk_launch_count", "qbk_workspace_bytes"])
+                                      ["qbk_fuse", "qbk_fuse_host", "qbk_last_error", "qbk_launch_census_begin", "qbk_launch_census_end", "qbk_launch_count", "qbk_workspace_bytes"])
     assert int(re.search(r"#define QBK_MAX_MEMBERS (\d+)", txt).group(1)) == bank.MAX_MEMBERS == 64
 
 

@@ -37,7 +37,7 @@ def cons_so():
 
 
 def test_library_exports_and_binds_every_declared_function(cons_so):
-    assert_exports_and_binds(consistency, HEADER, "qcs", cons_so, ["qcs_last_error", "qcs_launch_count", "qcs_nees", "qcs_nees_host"])
+    assert_exports_and_binds(consistency, HEADER, "qcs", cons_so, ["qcs_last_error", "qcs_launch_census_begin", "qcs_launch_census_end", "qcs_launch_count", "qcs_nees", "qcs_nees_host"])
 
 
 def test_summary_struct_is_eight_doubles_in_the_header_order():

@@ -76,12 +76,22 @@ class Run:
         self.c.close()
 
 
+def layout(monkeypatch, est_bias):
+    """est_bias = 0 runs on compact records (forced, as test_gpu_adapt.layout does: by default these small batches keep full records for
+    the workgroup-cooperative kernel, which est_bias = 1 runs on), so that both layouts' instantiations of k_score are held here; the
+    9-state full records are a row of tests/side_variant_table.py"""
+    if not est_bias:
+        monkeypatch.setenv("QLE_COMPACT", "1")
+
+
 # ------------------------------------------------------------------------------------------------ 1. configuration matrix
 @pytest.mark.parametrize("batch", [100, 65])
 @grid
-def test_scored_run_matches_the_tick_loop_and_the_reference(dtype, direct, est_bias, use_pfp, batch):
+def test_scored_run_matches_the_tick_loop_and_the_reference(dtype, direct, est_bias, use_pfp, batch, monkeypatch):
+    layout(monkeypatch, est_bias)
     r = Run(dtype, direct, est_bias, use_pfp, batch)
     c, io = r.c, r.io
+    assert bool(io._view().compact) == (est_bias == 0)
     seq = r.pack()
     # (a) one native call
     whole = io.scorer()
@@ -133,10 +143,12 @@ def test_scored_run_matches_the_tick_loop_and_the_reference(dtype, direct, est_b
 
 # ------------------------------------------------------------------------------------------------ 2. state untouched
 @pytest.mark.parametrize("dtype,est_bias,batch", [("f32", 1, 65), ("f64", 0, 100)])
-def test_scored_run_leaves_the_bits_of_the_plain_run(dtype, est_bias, batch):
+def test_scored_run_leaves_the_bits_of_the_plain_run(dtype, est_bias, batch, monkeypatch):
+    layout(monkeypatch, est_bias)
     rng = np.random.default_rng(3)
     r = Run(dtype, 1, est_bias, True, batch, mask=(rng.uniform(size=(len(MEAS), batch)) < 0.8).astype(np.uint8))
     c, io = r.c, r.io
+    assert bool(io._view().compact) == (est_bias == 0)
     seq = r.pack()
     io.run(seq)
     x1, P1 = c.ekf.get_state()

@@ -1,8 +1,8 @@
 """Device state I/O on the GPU (DeviceIO.set_state / snapshot / restore / gather / fork, stateio.Snapshot,
 BatchedRelativePoseEKF.gather_state; libqle_stateio.so: k_si_pack, k_si_copy; qle_mark_state_written of the tick library).
 
-B = 200 (three full tiles and a ragged tile of 8) and B = 70 (one tile and 6), fp32 and fp64, 15 states, 9 states with compact records,
-and 15 states with per-filter parameters.  Every comparison is bit for bit -- the feature moves and rounds words and computes nothing
+B = 200 (three full tiles and a ragged tile of 8) and B = 70 (one tile and 6), fp32 and fp64, 15 states, 9 states with full and with
+compact records, and 15 states with per-filter parameters.  Every comparison is bit for bit -- the feature moves and rounds words and computes nothing
 else: against the host `set_state` of the same values on a twin handle, against numpy fancy indexing of `get_state`, and, for what
 must not move, against every word of the record array read back through the device view (stateio_util.raw_read).
 """
@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 MR = dict(multirate_ekf=1, measurement_delay=3 / 400.0)
 # handle kinds: name -> (num_states, compact records, per-filter parameters)
-KINDS = {"full15": (15, False, False), "compact9": (9, True, False), "pfp15": (15, False, True)}
+KINDS = {"full15": (15, False, False), "full9": (9, False, False), "compact9": (9, True, False), "pfp15": (15, False, True)}
 GRID = [(d, k, B) for d in ("f32", "f64") for k in KINDS for B in (200, 70)]
 GRID_IDS = [f"{d}-{k}-B{B}" for d, k, B in GRID]
 SMALL = [(d, k) for d in ("f32", "f64") for k in KINDS]

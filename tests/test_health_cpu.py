@@ -34,7 +34,7 @@ def health_so():
 
 def test_library_exports_and_binds_every_declared_function(health_so):
     assert_exports_and_binds(health, HEADER, "qhl", health_so,
-                             ["qhl_and_masks", "qhl_health", "qhl_health_host", "qhl_last_error", "qhl_launch_count", "qhl_retire"])
+                             ["qhl_and_masks", "qhl_health", "qhl_health_host", "qhl_last_error", "qhl_launch_census_begin", "qhl_launch_census_end", "qhl_launch_count", "qhl_retire"])
 
 
 def test_seed_from_a_slot_is_exported_from_the_tick_library():

@@ -45,7 +45,7 @@ def imm_so():
 
 # ---------------------------------------------------------------- 1. header, exports, kernels, audit, resources
 def test_library_exports_and_binds_every_declared_function(imm_so):
-    assert_exports_and_binds(imm, HEADER, "qim", imm_so, ["qim_last_error", "qim_launch_count", "qim_mix", "qim_mix_host", "qim_update"])
+    assert_exports_and_binds(imm, HEADER, "qim", imm_so, ["qim_last_error", "qim_launch_census_begin", "qim_launch_census_end", "qim_launch_count", "qim_mix", "qim_mix_host", "qim_update"])
 
 
 def test_kernels_are_its_own_and_exactly_five(imm_so):

@@ -40,7 +40,7 @@ def look_so():
 # ---------------------------------------------------------------- 1. header, exports, kernels
 def test_library_exports_and_binds_every_declared_function(look_so):
     _, txt = assert_exports_and_binds(lookahead, HEADER, "qlk", look_so,
-                                      ["qlk_last_error", "qlk_launch_count", "qlk_lookahead", "qlk_lookahead_host", "qlk_workspace_bytes"])
+                                      ["qlk_last_error", "qlk_launch_census_begin", "qlk_launch_census_end", "qlk_launch_count", "qlk_lookahead", "qlk_lookahead_host", "qlk_workspace_bytes"])
     body = re.search(r"typedef struct qlk_coast \{(.*?)\} qlk_coast;", txt, flags=re.S).group(1)
     assert re.findall(r"(?:uint32_t|double)\s+([a-z_]+);", body) == [n for n, _ in lookahead.QlkCoast._fields_]
     assert int(re.search(r"#define QLK_MAX_HORIZON (\d+)", txt).group(1)) == lookahead.MAX_HORIZON == 4096

@@ -39,7 +39,7 @@ def score_so():
 
 def test_library_exports_and_binds_every_declared_function(score_so):
     _, txt = assert_exports_and_binds(score, HEADER, "qsc", score_so,
-                                      ["qsc_last_error", "qsc_launch_count", "qsc_run", "qsc_run_host", "qsc_score_tick", "qsc_summary"])
+                                      ["qsc_last_error", "qsc_launch_census_begin", "qsc_launch_census_end", "qsc_launch_count", "qsc_run", "qsc_run_host", "qsc_score_tick", "qsc_summary"])
     assert score.WORDS == int(re.search(r"#define QSC_WORDS (\d+)", txt).group(1)) == 40
     assert score.SUMS == int(re.search(r"#define QSC_SUMS (\d+)", txt).group(1)) == 30
 

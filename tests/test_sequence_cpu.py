@@ -30,7 +30,7 @@ def sequence_so():
 
 
 def test_library_exports_and_binds_every_declared_function(sequence_so):
-    _, txt = assert_exports_and_binds(sequence, HEADER, "qsq", sequence_so, ["qsq_last_error", "qsq_launch_count", "qsq_pack", "qsq_run"])
+    _, txt = assert_exports_and_binds(sequence, HEADER, "qsq", sequence_so, ["qsq_last_error", "qsq_launch_census_begin", "qsq_launch_census_end", "qsq_launch_count", "qsq_pack", "qsq_run"])
     assert sequence.CHUNK == int(re.search(r"#define QSQ_CHUNK (\d+)", txt).group(1)) == 32
 
 

@@ -37,7 +37,7 @@ def sio_so():
 # ---------------------------------------------------------------- 1. header, exports, kernels
 def test_library_exports_and_binds_every_declared_function(sio_so):
     _, txt = assert_exports_and_binds(stateio, HEADER, "qsi", sio_so,
-                                      ["qsi_copy", "qsi_copy_host", "qsi_last_error", "qsi_launch_count", "qsi_pack_state", "qsi_workspace_bytes"])
+                                      ["qsi_copy", "qsi_copy_host", "qsi_last_error", "qsi_launch_census_begin", "qsi_launch_census_end", "qsi_launch_count", "qsi_pack_state", "qsi_workspace_bytes"])
     assert re.search(r"#define QSI_F32 0\b", txt) and re.search(r"#define QSI_F64 1\b", txt)
     assert (stateio.QSI_F32, stateio.QSI_F64) == (devio.QDV_F32, devio.QDV_F64) == (0, 1)
 
