@@ -8,6 +8,7 @@ from .params import default_params, derive, load_yaml, make_params, set_fields  
 from . import replay  # noqa: F401
 from . import adapt  # noqa: F401
 from . import bank  # noqa: F401
+from . import budget  # noqa: F401
 from . import consistency  # noqa: F401
 from . import health  # noqa: F401
 from . import imm  # noqa: F401
@@ -16,3 +17,4 @@ from . import score  # noqa: F401
 from . import sequence  # noqa: F401
 from . import stateio  # noqa: F401
 from .sequence import DeviceSequence, SequenceResult  # noqa: F401
+from .budget import Budget  # noqa: F401

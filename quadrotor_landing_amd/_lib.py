@@ -180,7 +180,8 @@ def check(rc):
     return rc
 
 
-SIDE_LIBRARIES = {}   # stem -> SideLibrary, every one the package has made
+SIDE_LIBRARIES = {}   # stem -> SideLibrary, every one of the closed census (csrc/Makefile, SIDE) the package has made
+OPEN_LIBRARIES = {}   # stem -> SideLibrary outside it (csrc/Makefile, SIDE_OPEN): a census of its own, `SideLibrary.launch_census`
 
 
 class SideLibrary:
@@ -188,15 +189,18 @@ class SideLibrary:
     (`env` names the environment variable that overrides the in-tree path), what it exports (`symbols`, name -> (restype, argtypes)),
     `what` it is for (the error text when it is missing), the name of its `*_last_error`, and what has to be loaded in front of it.
     needs_tick_library: the library takes qle_params_derive from the tick library, which is loaded first so that it is the same copy
-    the handle uses (QLE_LIB included); `after`: side libraries it links, loaded before either."""
+    the handle uses (QLE_LIB included); `after`: side libraries it links, loaded before either.  closed_census: the library is one of
+    the Makefile's SIDE, whose kernels are the rows of the closed case table and which `side_launch_census` covers; False: it is one
+    of SIDE_OPEN, registered in `OPEN_LIBRARIES`, with a case table of its own."""
 
-    def __init__(self, stem, env, symbols, what, last_error, needs_tick_library=False, after=()):
+    def __init__(self, stem, env, symbols, what, last_error, needs_tick_library=False, after=(), closed_census=True):
         self.stem, self.path = stem, os.environ.get(env) or os.path.join(_HERE, f"libqle_{stem}.so")
         self.symbols, self.what, self.last_error = symbols, what, last_error
         self.prefix = last_error[:-len("_last_error")]
         self.needs_tick_library, self.after = needs_tick_library, tuple(after)
         self._handle = None
-        SIDE_LIBRARIES[stem] = self
+        self.closed_census = closed_census
+        (SIDE_LIBRARIES if closed_census else OPEN_LIBRARIES)[stem] = self
 
     def load(self):
         """The bound library, loaded on the first call; raises (never falls back) when it is missing."""

@@ -57,30 +57,7 @@ __device__ __forceinline__ T nees_eval(const T (&x)[16], T (&P)[120], const T (&
                                        uint32_t blocks, T (&e)[15], bool& pd)
 {
     constexpr int N = COMPACT ? 9 : 15;
-    // truth - (nom + static) with the rounding error of the sum carried (Knuth's two-sum): a bias error is orders of magnitude below
-    // the bias itself (1e-4 against 2e-2 for the gyroscope), and the plain form would leave it with the sum's rounding error, u |bias|,
-    // instead of u |e|.  The difference truth - sum is then exact or rounded relative to e.
-    auto bias_err = [](T truth, T nom, T stat) {
-        const T s = nom + stat;
-        const T bb = s - nom;
-        const T lo = (nom - (s - bb)) + (stat - bb);   // nom + stat = s + lo exactly
-        return (truth - s) - lo;
-    };
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        e[k] = xt[k] - x[k];
-        e[3 + k] = xt[3 + k] - x[3 + k];
-        e[9 + k] = bias_err(xt[10 + k], x[10 + k], ab_static[k]);
-        e[12 + k] = bias_err(xt[13 + k], x[13 + k], wb_static[k]);
-    }
-    {
-        const T qc[4] = {-x[6], -x[7], -x[8], x[9]}, qt[4] = {xt[6], xt[7], xt[8], xt[9]};
-        T dq[4], dth[3];
-        quat_mul(qc, qt, dq);    // EKF.cpp:448
-        quat_norm(dq);           // EKF.cpp:449
-        quat_log(dq, dth);       // EKF.cpp:450
-        e[6] = dth[0]; e[7] = dth[1]; e[8] = dth[2];
-    }
+    error_state<T>(x, xt, ab_static, wb_static, e);   // ekf_device.hpp: the two-sum bias errors, the attitude error of EKF.cpp:447-450
     // the marginal of the selected blocks as a full-size problem
     T y[N];
 #pragma unroll
@@ -105,23 +82,8 @@ __device__ __forceinline__ T nees_eval(const T (&x)[16], T (&P)[120], const T (&
 
 namespace qle {
 
-// row `row` of the truth tensor [B][16] as whole 16-byte pieces, cast to the compute dtype by the plain C cast
-template <typename T>
-__device__ __forceinline__ void load_truth(const void* __restrict__ xt, int64_t row, bool f64, T (&t)[16])
-{
-    if (f64) {
-        const qle_d2* s = reinterpret_cast<const qle_d2*>(static_cast<const double*>(xt) + row * 16);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { const qle_d2 v = s[k]; t[2 * k] = (T)v.x; t[2 * k + 1] = (T)v.y; }
-    } else {
-        const qle_f4* s = reinterpret_cast<const qle_f4*>(static_cast<const float*>(xt) + row * 16);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const qle_f4 v = s[k]; t[4 * k] = (T)v.x; t[4 * k + 1] = (T)v.y; t[4 * k + 2] = (T)v.z; t[4 * k + 3] = (T)v.w; }
-    }
-}
-
 // One lane per filter, one wave per workgroup (a workgroup is one 64-filter tile).  Reads the state, never writes it.
-// xt [B][16] of float32 / float64 (true_f64), mask [B] or null; nees [B], err [B][n_err] of dst dtype and partials [tiles][8] (fp64):
+// xt [B][16] of float32 / float64 (true_f64; load_truth, ekf_layout.hpp), mask [B] or null; nees [B], err [B][n_err] of dst dtype and partials [tiles][8] (fp64):
 // any may be null (wave-uniform).  fp64 holds 240 registers of P: one wave per SIMD, as k_predict<double>; fp32 fits two.
 template <typename T, bool PFP, bool COMPACT>
 __global__ __launch_bounds__(kTile, sizeof(T) == 8 ? 1 : 2) void k_nees(const T* __restrict__ st, const void* __restrict__ xt, int64_t B,

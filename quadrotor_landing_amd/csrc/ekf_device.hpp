@@ -320,6 +320,40 @@ __device__ __forceinline__ void quat_mul(const T (&a)[4], const T (&b)[4], T (&o
     o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
 }
 
+// The error of a state against a truth, in the filter's own error-state convention -- what the read-only diagnostics that hold a filter
+// to a truth share (nees_eval, ekf_consistency.hpp; budget_lane, ekf_budget.hpp).  e = truth (-) estimate (15 words: r, v, th, ab, wb) of
+// state x against truth row xt (r, v, q xyzw, ab, wb; the TOTAL biases): e_r = r_true - r, e_v = v_true - v,
+// e_th = log(norm(q^-1 (x) q_true)) -- the form of the attitude innovation (EKF.cpp:447-450) with the w < -0.75 flip of quaternion_norm --
+// e_ab = ab_true - (ab_nom + ab_static), e_wb = wb_true - (wb_nom + wb_static).
+template <typename T>
+__host__ __device__ __forceinline__ void error_state(const T (&x)[16], const T (&xt)[16], const T (&ab_static)[3], const T (&wb_static)[3], T (&e)[15])
+{
+    // truth - (nom + static) with the rounding error of the sum carried (Knuth's two-sum): a bias error is orders of magnitude below
+    // the bias itself (1e-4 against 2e-2 for the gyroscope), and the plain form would leave it with the sum's rounding error, u |bias|,
+    // instead of u |e|.  The difference truth - sum is then exact or rounded relative to e.
+    auto bias_err = [](T truth, T nom, T stat) {
+        const T s = nom + stat;
+        const T bb = s - nom;
+        const T lo = (nom - (s - bb)) + (stat - bb);   // nom + stat = s + lo exactly
+        return (truth - s) - lo;
+    };
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        e[k] = xt[k] - x[k];
+        e[3 + k] = xt[3 + k] - x[3 + k];
+        e[9 + k] = bias_err(xt[10 + k], x[10 + k], ab_static[k]);
+        e[12 + k] = bias_err(xt[13 + k], x[13 + k], wb_static[k]);
+    }
+    {
+        const T qc[4] = {-x[6], -x[7], -x[8], x[9]}, qt[4] = {xt[6], xt[7], xt[8], xt[9]};
+        T dq[4], dth[3];
+        quat_mul(qc, qt, dq);    // EKF.cpp:448
+        quat_norm(dq);           // EKF.cpp:449
+        quat_log(dq, dth);       // EKF.cpp:450
+        e[6] = dth[0]; e[7] = dth[1]; e[8] = dth[2];
+    }
+}
+
 // Rotation matrix of a unit quaternion (Eigen toRotationMatrix, EKF.cpp:359,429).
 template <typename T>
 __device__ __forceinline__ void quat_to_rot(const T (&q)[4], T (&C)[9])

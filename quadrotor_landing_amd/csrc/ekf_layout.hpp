@@ -344,6 +344,22 @@ __device__ __forceinline__ void put(void* dst, int64_t k, T v, bool dst_f64)
     else static_cast<float*>(dst)[k] = (float)v;
 }
 
+// row `row` of a truth tensor [rows][16] (the diagnostics against a truth: k_nees, ekf_consistency.hpp; k_budget, ekf_budget.hpp) as
+// whole 16-byte pieces, cast to the compute dtype by the plain C cast
+template <typename T>
+__device__ __forceinline__ void load_truth(const void* __restrict__ xt, int64_t row, bool f64, T (&t)[16])
+{
+    if (f64) {
+        const qle_d2* s = reinterpret_cast<const qle_d2*>(static_cast<const double*>(xt) + row * 16);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { const qle_d2 v = s[k]; t[2 * k] = (T)v.x; t[2 * k + 1] = (T)v.y; }
+    } else {
+        const qle_f4* s = reinterpret_cast<const qle_f4*>(static_cast<const float*>(xt) + row * 16);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const qle_f4 v = s[k]; t[4 * k] = (T)v.x; t[4 * k + 1] = (T)v.y; t[4 * k + 2] = (T)v.z; t[4 * k + 3] = (T)v.w; }
+    }
+}
+
 // (HIP compilers only: a host compiler that reads this header for the layout arithmetic, tests/cpp/devio_index_harness.cpp, has no
 // declaration of __syncthreads.)
 #if defined(__HIPCC__)

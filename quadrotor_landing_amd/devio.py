@@ -17,6 +17,11 @@ Filter consistency against a truth that lives on the GPU: `nees(x_true, ...)` re
 squared e^T P^-1 e and an eight-double batch summary as device tensors (consistency.py, libqle_consistency.so: two read-only kernels,
 no synchronisation).
 
+The error budget of a Monte-Carlo sweep (budget.py, libqle_budget.so): `budget(x_true, group_tiles=...)` returns per group of filters
+the count, sum e, sum e e^T and sum P as 256 float64 values -- bias, error covariance and reported covariance of every state -- from
+two read-only launches, deterministic to the bit and additive over shards; `budget_run(seq, x_true_seq, every)` gives it at every
+e-th tick of a sequence.
+
 Filter lifecycle from device tensors (health.py, libqle_health.so, and qle_initialize_state_slot of the tick library):
 `seed(z, mask)` seeds filters from tag poses on the GPU, `health(...)` classifies every filter in one read-only launch (non-finite,
 not positive definite, quaternion norm, sigma limits), `retire(mask)` makes filters "uninitialised" so that ticks skip them, and
@@ -62,6 +67,7 @@ import math
 from . import _tensors as _t
 from . import adapt as _adapt
 from . import bank as _bank
+from . import budget as _budget
 from . import gate as _gate
 from . import health as _health
 from . import imm as _imm
@@ -253,6 +259,30 @@ class DeviceIO(DeviceRecords):
         x_true_seq [J,B,16] -- J = n // e slices, slice j after tick t0 + (j + 1) e - 1.  dtype: of nis, report and nees (None: the
         handle's).  Returns a `sequence.SequenceResult` of device tensors; asynchronous, no synchronisation."""
         return _seqm.run(self, seq, t0, n, chi2_max, return_nis, trace_every, trace, x_true_seq, blocks, chi2_hi, dtype)
+
+    def budget_run(self, seq, x_true_seq, every, t0=0, n=None, mask=None, group_tiles=None, **run_kw):
+        """The error budget at every `every`-th tick of a run: J = n // every times `run(seq, t0 + j every, every, **run_kw)` followed by
+        `budget(x_true_seq[j], mask, group_tiles, out=sums[j])` -- the ticks and the layout of x_true_seq [J,B,16] are those of
+        `run(..., trace_every=every, trace=("nees",), x_true_seq=...)`: slice j is taken after tick t0 + (j + 1) every - 1; the ticks
+        of a remainder n % every are not run.  Returns a `budget.Budget` over sums [J,G,256]: 256 doubles per group and slice,
+        whatever the batch.  J native calls of `run`, a Python loop (run_kw: its chi2_max and the like; no trace);
+        asynchronous, no synchronisation.  The state after it is the state after one `run` over the J every ticks, bit for bit."""
+        if isinstance(every, bool) or int(every) != every or int(every) < 1:
+            raise ValueError(f"every must be an integer >= 1 (got {every})")
+        every = int(every)
+        if set(run_kw) & {"trace_every", "trace", "x_true_seq"}:
+            raise ValueError("budget_run takes no trace: the budget is what it takes every `every` ticks")
+        t0, n = _seqm.check_window(t0, n, seq.n_ticks)
+        J, B = n // every, self.batch
+        self._check(x_true_seq, "x_true_seq", (J, B, 16))
+        self._check_mask(mask)
+        _, G = _budget.groups(B, group_tiles)
+        _budget.budget_lib()   # a missing library is an error before anything is allocated or run
+        sums = self._alloc([(J, G, _budget.WORDS)], "float64")[0]
+        for j in range(J):
+            self.run(seq, t0 + j * every, every, **run_kw)
+            self.budget(x_true_seq[j], mask=mask, group_tiles=group_tiles, out=sums[j])
+        return _budget.Budget(sums)
 
     # ---- innovation scoring for noise sweeps
     def scorer(self):

@@ -337,6 +337,11 @@ class BatchedRelativePoseEKF:
         velocity, so the velocity block is left out): blocks r, theta, ab, wb, or r, theta for a filter without bias states.
         The generator's bias truth is the unknown part of the IMU bias; the total true bias adds the static (known) biases, per filter
         where per-filter parameters are in force."""
+        xt = self._synth_truth_rows(inputs)
+        return self.nees(xt, blocks="r+theta+ab+wb" if self.num_states == 15 else "r+theta", chi2_hi=chi2_hi)
+
+    def _synth_truth_rows(self, inputs):
+        """the generator's truth at the end of `inputs` as x_true rows [B,16] (no velocity: zeros), with the total true biases"""
         pose, bias = self.synth_truth(inputs)
         if _t.device_view(self).filter_params:
             static = self.get_filter_params()[:, 12:18]
@@ -344,7 +349,33 @@ class BatchedRelativePoseEKF:
             static = np.array(list(self.params.ab_static) + list(self.params.wb_static))[None, :]
         xt = np.zeros((self.batch, 16))
         xt[:, 0:3] = pose[:, 0:3]; xt[:, 6:10] = pose[:, 3:7]; xt[:, 10:16] = bias + static
-        return self.nees(xt, blocks="r+theta+ab+wb" if self.num_states == 15 else "r+theta", chi2_hi=chi2_hi)
+        return xt
+
+    # ---- the per-component error budget against a truth (include/qle_budget.h)
+    def error_budget(self, x_true, mask=None, group_tiles=None):
+        """The error budget of the batch against the truth x_true [B,16] (the layout of `nees`), or [16] / [1,16]: one reference row
+        for every filter.  Host arrays in and out; the arithmetic runs on the device (k_budget, k_budget_reduce), the state is
+        unchanged.  Returns a `budget.Budget` over numpy arrays: sums [G,256] per group of group_tiles 64-filter tiles (None: one
+        group), err [B,n] and status [B] (0 off, 1 counted, 2 on but not finite); its mean, cov, P_mean, var_ratio, rms and sigma
+        are the budget.  The bits are those of `DeviceIO.budget` on the same values."""
+        from . import budget as bg
+        B, n = self.batch, self.num_states
+        xt = np.ascontiguousarray(x_true, np.float64)
+        rows = 1 if xt.shape in ((16,), (1, 16)) else B
+        xt = _f64(xt.reshape(1, 16) if rows == 1 else xt, (rows, 16))
+        m = _u8(mask, (B,))
+        gt, G = bg.groups(B, group_tiles)
+        K = bg.budget_lib()
+        view = _t.device_view(self)
+        sums = np.empty((G, bg.WORDS)); err = np.empty((B, n)); status = np.empty(B, np.uint8)
+        bg.bcheck(K.qbg_budget_host(C.byref(view), C.byref(self.params), _dp(xt), rows, None if m is None else m.ctypes.data_as(_pu8), gt,
+                                    _dp(sums), _dp(err), status.ctypes.data_as(_pu8)))
+        return bg.Budget(sums, err, status)
+
+    def synth_budget(self, inputs, group_tiles=None):
+        """error_budget() against the generator's truth at the end of `inputs`, beside `synth_nees`.  The generator keeps no velocity:
+        the velocity components of the budget are the estimate's own (against zero) and mean nothing."""
+        return self.error_budget(self._synth_truth_rows(inputs), group_tiles=group_tiles)
 
     # ---- innovation scoring for noise sweeps (include/qle_score.h)
     def score(self, inputs, t0, n):

@@ -1,4 +1,4 @@
-"""The read-only consumers of a `qle_device_view`: `state`, `report`, `health`, `nees`, once, for every view they are read from.
+"""The read-only consumers of a `qle_device_view`: `state`, `report`, `health`, `nees`, `budget`, once, for every view they are read from.
 
 `DeviceRecords` is what a handle's records, a forecast of them and a fused estimate of them have in common: the handle they descend
 from (parameters, device, dtype, num_states -- read, never written), a batch, and a `_view()` the subclass defines.
@@ -8,6 +8,7 @@ from (parameters, device, dtype, num_states -- read, never written), a batch, an
 import ctypes as C
 
 from . import _tensors as _t
+from . import budget as _budget
 from . import consistency as _cons
 from . import health as _health
 from ._lib import QLE_F32
@@ -136,6 +137,39 @@ class DeviceRecords:
                                     None if mask is None else mask.data_ptr(), bits, chi2_hi, nees.data_ptr(),
                                     None if err is None else err.data_ptr(), summary.data_ptr(), _t.FLOATS[dn]))
         return (nees, err, summary) if return_err else (nees, summary)
+
+    # ---- the per-component error budget against a truth
+    def budget(self, x_true, mask=None, group_tiles=None, return_err=False, return_status=False, dtype=None, out=None):
+        """The error budget of the batch against x_true, per group of filters: a `budget.Budget` over sums [G,256] (float64 device
+        tensor: the count, sum e, sum e e^T and sum P of include/qle_budget.h), from which it derives mean, mse, cov, P_mean, var_ratio,
+        rms and sigma on the device.  e is the error of `nees`; x_true is [B,16] (float32 or float64), or [16] / [1,16]: one reference
+        row for every filter, the dispersion of the ensemble about a common point.  mask [B] (uint8 / bool; None = all).
+        group_tiles: a group is that many consecutive 64-filter tiles, G = ceil(ceil(B / 64) / group_tiles); None or 0 = one group.
+        A filter is counted when its mask is not 0, it has a state and its error and covariance are finite.  return_err: the
+        Budget's `err` [B,n] (dtype: None = the handle's) holds e, 0 where the filter is off; return_status: its `status` [B] (uint8)
+        holds 0 off, 1 counted, 2 on but not finite.  out: a float64 device tensor [G,256] the sums are written to, for example a
+        slice of a [J,G,256] buffer.  Two read-only launches; asynchronous, no synchronisation, deterministic to the bit, and additive:
+        the sums of shards that are whole groups are the groups' sums of the whole batch.  Works on a forecast, a snapshot and a
+        fused view (x_true [G,16] there) as `nees` does."""
+        B, n = self.batch, self.ekf.num_states
+        shape = tuple(getattr(x_true, "shape", ()))
+        rows = 1 if shape in ((16,), (1, 16)) else B
+        src = self._check(x_true, "x_true", shape if rows == 1 else (B, 16))
+        self._check_mask(mask)
+        gt, G = _budget.groups(B, group_tiles)
+        dn = self._out_dtype(dtype)
+        if out is not None:
+            self._check(out, "out", (G, _budget.WORDS), ("float64",), align=8)
+        K = _budget.budget_lib()
+        view = self._view()
+        sums = self._alloc([(G, _budget.WORDS)], "float64")[0] if out is None else out
+        err = self._alloc([(B, n)], dn)[0] if return_err else None
+        status = self._alloc([(B,)], "uint8")[0] if return_status else None
+        with self._ordered(view, x_true, mask, out):
+            _budget.bcheck(K.qbg_budget(C.byref(view), C.byref(self.ekf.params), x_true.data_ptr(), _t.FLOATS[src], rows,
+                                        None if mask is None else mask.data_ptr(), gt, sums.data_ptr(),
+                                        None if err is None else err.data_ptr(), _t.FLOATS[dn], None if status is None else status.data_ptr()))
+        return _budget.Budget(sums, err, status)
 
 
 class ViewRecords(DeviceRecords):
