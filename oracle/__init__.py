@@ -165,6 +165,29 @@ def structured_run_batch(p, x, P, u, z=None, mask=None, dtype="f64", levels=True
     return x, P.reshape(B, n, n)
 
 
+def structured_update_batch(p, x, P, z, R=None, dtype="f64", route="levels"):
+    """One stand-alone correction per filter with the engine's headers compiled for the host: x [B,16], P [B,n,n] (copied), z [B,7],
+    R [B,6] per-filter tag noise (None = p.R) -> (x_hat, P_hat).  route: "levels" = the sequential update on the flat covariance,
+    "packed" = the same between the unpack and pack of the packed multirate replay (shows only that cov_unpack / cov_pack lose nothing:
+    bit for bit "levels"), "split" = the batch-form correction on the split
+    covariance (the fp64 multirate replay)."""
+    L = _structured_lib()
+    n = p.num_states
+    x = np.array(x, dtype=np.float64, order="C").reshape(-1, 16)
+    B = x.shape[0]
+    P = np.array(P, dtype=np.float64, order="C").reshape(B, n * n)
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(B, 7)
+    Rp = None
+    if R is not None:
+        R = np.ascontiguousarray(R, dtype=np.float64).reshape(B, 6)
+        Rp = _p(R)
+    L.orc_structured_update_batch.argtypes = [C.POINTER(OrcParams), C.c_int64, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), _i, _i]
+    L.orc_structured_update_batch.restype = C.c_int64
+    done = L.orc_structured_update_batch(C.byref(p), B, _p(x), _p(P), _p(z), Rp, 0 if dtype == "f32" else 1, {"levels": 1, "packed": 3, "split": 4}[route])
+    assert done == B, done
+    return x, P.reshape(B, n, n)
+
+
 _lib = None
 
 

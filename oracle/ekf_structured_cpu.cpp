@@ -237,7 +237,57 @@ static int64_t quad_run_batch_t(const orc_params* p, int64_t B, int64_t Tn, doub
     return B * Tn;
 }
 
+// ---- one correction, no predict in front (tests/test_ratio_cpu.py) --------------------------------------------
+// route 1: the sequential update on the flat covariance (what k_update and the levelled tick run); 3: the same between cov_unpack and
+// cov_pack, as the packed multirate replay runs it; 4: the batch-form correction on the split covariance (the fp64 multirate replay).
+// R: per-filter noise [B, 6], or null for the shared p->R.
+template <typename T>
+static int64_t update_batch_t(const orc_params* p, int64_t B, double* x, double* P, const double* z, const double* R, int route)
+{
+    const int n = p->num_states;
+    const DevParams<T> dp = to_dev<T>(p);
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < B; ++i) {
+        Noise<T> nz;
+        for (int k = 0; k < 12; ++k) nz.Q[k] = dp.Q[k];
+        for (int k = 0; k < 3; ++k) { nz.ab_static[k] = dp.ab_static[k]; nz.wb_static[k] = dp.wb_static[k]; }
+        for (int k = 0; k < 6; ++k) nz.R[k] = R ? (T)R[6 * i + k] : dp.R[k];
+        T xs[16], Pp[120], obs[7], zz[7];
+        for (int k = 0; k < 16; ++k) xs[k] = (T)x[16 * i + k];
+        for (int k = 0; k < 7; ++k) zz[k] = (T)z[7 * i + k];
+        const double* Pi = P + (int64_t)n * n * i;
+        for (int a = 0; a < 15; ++a)
+            for (int b = a; b < 15; ++b) Pp[sidx(a, b)] = (a < n && b < n) ? (T)(0.5 * (Pi[a * n + b] + Pi[b * n + a])) : T(0);
+        if (route == 4) {
+            ArrayTop<T> top;
+            T lo[kLoWords];
+            split_from_flat<T>(Pp, top, lo);
+            auto none7 = [](const T (&)[7]) {};
+            if (p->direct_orien_method) ekf_update_split<T, true>(dp, nz, xs, top, lo, zz, none7);
+            else ekf_update_split<T, false>(dp, nz, xs, top, lo, zz, none7);
+            split_to_flat<T>(top, lo, Pp);
+        } else {
+            PackedCov<T> Sb;
+            if (route == 3) { cov_pack<T>(Pp, Sb); cov_unpack<T>(Sb, Pp); }
+            if (p->direct_orien_method) ekf_update<T, true>(dp, nz, xs, Pp, zz, obs);
+            else ekf_update<T, false>(dp, nz, xs, Pp, zz, obs);
+            if (route == 3) { cov_pack<T>(Pp, Sb); cov_unpack<T>(Sb, Pp); }
+        }
+        for (int k = 0; k < 16; ++k) x[16 * i + k] = (double)xs[k];
+        double* Po = P + (int64_t)n * n * i;
+        for (int a = 0; a < n; ++a)
+            for (int b = 0; b < n; ++b) Po[a * n + b] = (double)Pp[sidx(a, b)];
+    }
+    return B;
+}
+
 extern "C" {
+// One stand-alone correction per filter (update_batch_t above).  dtype 0 = fp32 arithmetic, 1 = fp64.
+int64_t orc_structured_update_batch(const orc_params* p, int64_t B, double* x, double* P, const double* z, const double* R, int dtype, int route)
+{
+    if (route != 1 && route != 3 && route != 4) return -1;
+    return dtype == 0 ? update_batch_t<float>(p, B, x, P, z, R, route) : update_batch_t<double>(p, B, x, P, z, R, route);
+}
 // The engine's quaternion_exp (ekf_device.hpp: half-angle series with halving / doubling beyond pi/4) for n rotation vectors.
 void orc_structured_quat_exp(const double* v, double* q, int64_t n, int dtype)
 {

@@ -322,7 +322,9 @@ def test_randomized_configurations_short_runs_vs_oracle(dtype):
         if dtype == "f64":
             assert_state_close(xg, Pg, xr, Pr, 1e-9, 1e-11, 1e-9)
         else:   # 8 ticks, 4-5 corrections with innovations of up to 170 degrees (the logarithm next to pi), noise levels over four
-            #         decades (cond(S) up to 1e4): the one deliberately ill-conditioned fp32 comparison; measured 1.1e-3 / 1.1e-4 / 3.2e-4
+            #         decades (cond(S) up to 1e4): an ill-conditioned fp32 comparison at one fixed tolerance; measured 1.1e-3 / 1.1e-4 /
+            #         3.2e-4.  The axis itself -- prior-to-noise ratios from 1 to 1e8, the bound scaled by u (1 + rho) against an
+            #         80-digit truth -- is walked by tests/test_ratio_cpu.py and tests/test_gpu_ratio.py (tests/tolerances_ratio.md)
             assert_state_close(xg, Pg, xr, Pr, 5e-3, 5e-3, 5e-4, ptol=2e-3)
         ekf.close()
 
